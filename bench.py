@@ -50,6 +50,9 @@ Extra objects in the JSON line:
                   density, a bounded sample on this box's cores; `tuned` = its free-order SIMD build) and `gpu_over_cpu`, also where it
                   is below 1 (config 4: a 10-dimensional host callback is faster on 16 CPU threads than through the GPU).
 
+``--dump-outputs DIR`` writes, after the timed steps and outside the timed region, what they computed: every chain's latest draw
+and its statistics, float64 ``.npy`` files (``dump_outputs``).  With the same arguments the inputs are the same from run to run.
+
 Launching: under torch.distributed.run (RANK in the environment) this process is one rank.  WITHOUT it, `--gpus N` with
 N > 1 re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`,
 one rank per GPU, and fails loudly when fewer than N GPUs are visible.
@@ -100,6 +103,8 @@ def parse(argv=None):
     p.add_argument("--no-config5", action="store_true", help="skip the config-5 shard leg (10 000 dimensions, roofline + trace gather)")
     p.add_argument("--config5-dim", type=int, default=10000)
     p.add_argument("--config5-launches", type=int, default=10)
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what they computed (every chain's latest draw and its statistics) as DIR/<name>.npy")
     p.add_argument("--engine-stub", default="", help="TEST PLUMBING ONLY: path of a module that stands in for nutpie_amd._lib (no GPU, gloo); "
                    "the line it prints is marked stub and measures nothing")
     return p.parse_args(argv)
@@ -512,6 +517,48 @@ def timed_launches(env, smp, K, total_draws):
         raise InvalidRegion("bench.py: a chain ran out of draws inside the timed region" + ("" if bad else " (on another rank)") +
                             " — the measurement is invalid; use fewer --steps")
     return t1 - t0, float(total_leapfrogs(smp) - n0), kernel_ms, prog
+
+
+DUMP_STATS = {"depth": np.int64, "n_steps": np.int64, "index_in_trajectory": np.int64, "diverging": np.bool_, "maxdepth_reached": np.bool_,
+              "energy": np.float64, "energy_error": np.float64, "logp": np.float64, "step_size": np.float64, "mean_tree_accept": np.float64}
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(env, smp, prog, out_dir):
+    """``--dump-outputs DIR``: what the timed launches handed to a caller, written after them (untimed) as float64 ``.npy`` files —
+    every local chain's latest finished draw (``last_draw [chains, dim]``), its index and its statistics (``last_<stat> [chains]``),
+    and each chain's leapfrog total (``total_leapfrogs``).  The workload is seeded, so two builds run with the same arguments can be
+    compared file by file.  Where ``last_draw`` would pass DUMP_MAX_BYTES, a fixed, seeded sample of chains is written, and
+    ``chain_ids`` names them.  Under torch.distributed.run every rank writes its own chains, with the suffix ``_rank<r>``."""
+    env.sync()
+    fin = np.array([p.finished_draws for p in prog], dtype=np.int64)
+    n = len(fin)
+    last = np.maximum(fin - 1, 0)
+    dim = int(smp.dim)
+    rows = np.arange(n)
+    if n * dim * 8 > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=max(1, DUMP_MAX_BYTES // (dim * 8)), replace=False))
+    out = {"chain_ids": (rows + int(getattr(smp, "_chain_offset", getattr(smp, "offset", 0)))).astype(np.float64),
+           "last_draw_index": last[rows].astype(np.float64), "total_leapfrogs": np.array([p.total_num_steps for p in prog], dtype=np.float64)[rows]}
+    if env.stub:
+        out["last_draw"] = smp._copy("draws", np.float64, vec=True)[rows, last[rows]]
+    elif smp.device_ptr("draws"):
+        from nutpie_amd.distributed import device_tensor
+
+        torch = env.torch
+        d = device_tensor(smp.device_ptr("draws"), (n, int(smp.total_draws), dim), "float64", env.device)
+        sel = torch.as_tensor(rows, device=d.device)
+        out["last_draw"] = d[sel, torch.as_tensor(last[rows], device=d.device)].cpu().numpy()
+        del d
+    for k, dt in DUMP_STATS.items():   # (the engine's dtypes: nutpie_amd._lib._STAT_DTYPES)
+        out["last_" + k] = smp._copy(k, dt)[rows, last[rows]].astype(np.float64)
+    for k, v in out.items():
+        if k.startswith("last_"):
+            v[fin[rows] == 0] = np.nan   # (no draw finished yet: nothing to report; cannot happen after the warm-up)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{env.rank}" if env.world > 1 else ""
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def config5_shard(env, args):
@@ -929,6 +976,11 @@ def main(argv=None):
     args = parse(argv)
     if "RANK" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args, argv))
+    # stdout is for the ONE JSON line: everything else that reaches fd 1 while the bench runs (RCCL prints a version banner through
+    # C stdio when a communicator is created, also lazily inside a later collective) goes to stderr; the line goes to a copy of fd 1
+    sys.stdout.flush()
+    result_fd = os.dup(1)
+    os.dup2(2, 1)
     env = Env(args)
     hip, world, rank, device, dist = env.hip, env.world, env.rank, env.device, env.dist
 
@@ -984,6 +1036,8 @@ def main(argv=None):
     kernel_ms = kernel_ms_sum / world
     draws_stored = int(sum(p.finished_draws for p in prog)) if store else 0
     draws_in_region = env.all_sum([float(sum(p.finished_draws for p in prog) - draws0)])[0]
+    if args.dump_outputs:
+        dump_outputs(env, smp, prog, args.dump_outputs)
     smp.close()
 
     avg_kernel_s = kernel_ms / 1000.0 / K
@@ -1032,8 +1086,7 @@ def main(argv=None):
             if "value" in tuned:
                 out["gpu_over_cpu_tuned"] = out["value"] / tuned["value"]
     if rank == 0:
-        # (RCCL prints a version banner through C stdio when its first communicator is created; flush it BEFORE the line, so
-        #  that the JSON line is the last thing on stdout)
+        # (what C stdio still holds goes out first, to stderr: see the top of main)
         try:
             import ctypes
 
@@ -1041,7 +1094,9 @@ def main(argv=None):
         except Exception:
             pass
         sys.stdout.flush()
-        print(json.dumps(out), flush=True)
+        with os.fdopen(os.dup(result_fd), "w") as f:
+            f.write(json.dumps(out) + "\n")
+    os.close(result_fd)
     if env.dist is not None:
         env.dist.barrier()
         env.dist.destroy_process_group()

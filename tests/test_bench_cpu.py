@@ -130,6 +130,28 @@ def test_stub_gather_is_in_global_chain_order():
     assert c5["gather"]["arrays"]["draws"][0] == 4 and c5["gather"]["arrays"]["draw_mean"] == [4, 32]
 
 
+def test_dump_outputs_writes_every_chains_latest_draw(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps, every chain's latest draw and its statistics as float64 .npy files; the same
+    arguments give the same files."""
+    import numpy as np
+
+    dumps = []
+    for run in ("a", "b"):
+        r, out, _ = _run_bench("--engine-stub", STUB, "--chains", "4", "--dim", "16", "--no-config5", "--steps", "2", "--warmup", "1",
+                               "--dump-outputs", str(tmp_path / run))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert r.stdout.count("\n") == 1 and r.stdout.startswith("{")     # stdout holds the result line and nothing else
+        dumps.append({p.name: np.load(p) for p in (tmp_path / run).glob("*.npy")})
+    a, b = dumps
+    assert set(a) == set(b) and {"last_draw.npy", "last_draw_index.npy", "last_logp.npy", "chain_ids.npy"} <= set(a)
+    assert all(v.dtype == np.float64 and np.array_equal(v, b[k]) for k, v in a.items())
+    assert a["last_draw.npy"].shape == (4, 16) and list(a["chain_ids.npy"]) == [0, 1, 2, 3]
+    # the stub's draw t of chain c is c + 1e-3 t: (warm-up to draw 400 in 10-launch batches + 1 + 2 launches) x 8 leapfrogs / 4 per draw
+    idx = a["last_draw_index.npy"]
+    assert np.all(idx >= 400) and np.allclose(a["last_draw.npy"], (np.arange(4) + 1e-3 * idx)[:, None])
+
+
 def test_gpus_n_refuses_when_fewer_gpus_are_visible():
     import torch
 
