@@ -191,6 +191,8 @@ def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verb
     nv = ((int(ndim) + 127) // 128 + waves - 1) // waves   # chunks of 128 dimensions per wave
     src = generated_source(user_source, layout)
     deps = [os.path.join(_CSRC, f) for f in ("kernels.hip", "engine_types.h", "dense_tile.h")] + [os.path.join(_INCLUDE, "nphip_spec.h")]
+    if '#include "chain_linalg.h"' in user_source:
+        deps.append(os.path.join(_CSRC, "chain_linalg.h"))
     h = hashlib.sha256()
     h.update(src.encode())
     for d in deps:

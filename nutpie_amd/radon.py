@@ -466,3 +466,95 @@ def radon_symbolic_model(data=None):
     z = (y - mu) / sig
     m.add_logp((-0.5 * (z * z) - S.log(sig)).sum())
     return m
+
+
+# ------------------------------------------------------------------------------------------------ correlated varying effects
+def synthetic_correlated_radon_data(n_counties=N_COUNTIES, n_obs=N_OBS, rho=-0.5, sd=(0.45, 0.4), seed=20261015):
+    """Radon-shaped data whose county intercepts and floor slopes are drawn TOGETHER: a bivariate normal with standard deviations
+    ``sd`` and correlation ``rho`` (the next model of the radon tutorial).  A floor measurement in 40 % of the houses."""
+    rng = np.random.default_rng(seed)
+    county_idx = rng.integers(0, n_counties, size=n_obs)
+    county_idx[:n_counties] = np.arange(n_counties)
+    floor = (rng.uniform(size=n_obs) < 0.4).astype(np.float64)
+    cov = np.array([[sd[0] ** 2, rho * sd[0] * sd[1]], [rho * sd[0] * sd[1], sd[1] ** 2]])
+    ab = rng.multivariate_normal([0.0, 0.0], cov, size=n_counties)          # [county, (intercept, slope)]
+    y = 1.3 + ab[county_idx, 0] + (-0.6 + ab[county_idx, 1]) * floor + 0.5 * rng.normal(size=n_obs)
+    return {"county_idx": county_idx, "floor": floor, "log_radon": y, "rho": rho}
+
+
+def correlated_radon_model(data=None, eta=2.0):
+    """County intercepts and floor slopes with an LKJ-Cholesky covariance (:mod:`nutpie_amd.symbolic`): ``ab`` (2 x counties, every
+    column one county's (intercept, slope)) ~ MvNormal(0, L L^T) — one factor and two triangular solves per evaluation, on the chain's
+    wave —, gathered into the observations.  ``intercept`` ~ N(0, 10), ``floor_effect`` ~ N(0, 2), ``sigma`` ~ HalfNormal(1.5),
+    ``chol`` ~ LKJCholeskyCov(2, eta, HalfNormal(1)).  Flat vector: intercept, floor_effect, sigma_log__, the packed factor (3),
+    ab (2 n, row-major)."""
+    from nutpie_amd import symbolic as S
+
+    d = data or synthetic_correlated_radon_data()
+    n = int(np.max(d["county_idx"])) + 1
+    m = S.Model()
+    intercept = m.param("intercept")
+    fe = m.param("floor_effect")
+    sig = m.param("sigma", lower=0.0)
+    L, sd = m.lkj_cholesky_cov("chol", 2, eta, lambda s: S.halfnormal_lpdf(s, 1.0))
+    m.dim("county", n)
+    ab = m.param("ab", dims=("chol_k", "county"))
+    prod = m.product("chol_k", "county")
+    y = m.data("y", d["log_radon"], dim="obs")
+    fl = m.data("floor", d["floor"], dim="obs")
+    ci = np.asarray(d["county_idx"])
+    a_of = m.index("a_of_obs", ci, dim="obs", into=prod.name)
+    b_of = m.index("b_of_obs", ci + n, dim="obs", into=prod.name)
+    m.deterministic("chol_sd", sd)
+    m.deterministic("chol_corr", S.elem(L, 2) / S.elem(sd, 1))        # L[1][0] / sd[1]
+    m.add_logp(S.normal_lpdf(intercept, 0.0, 10.0) + S.normal_lpdf(fe, 0.0, 2.0) + S.halfnormal_lpdf(sig, 1.5))
+    m.add_logp(S.mvnormal_lpdf(ab, 0.0, chol=L))
+    mu = intercept + ab[a_of] + fl * (fe + ab[b_of])
+    m.add_logp(S.normal_lpdf(y, mu, sig).sum())
+    return m
+
+
+def correlated_radon_torch_density(data=None, eta=2.0, device="cpu"):
+    """The same log-density as :func:`correlated_radon_model`, written as a batched torch function of the same flat vector (its
+    eager form: ``from_torchfunc(D, lambda: autograd_logp(logp))``).  Returns ``(D, logp)``."""
+    import math
+
+    import torch
+    from torch.distributions import MultivariateNormal
+
+    from nutpie_amd.symbolic import _lkj_log_norm
+
+    d = data or synthetic_correlated_radon_data()
+    n = int(np.max(d["county_idx"])) + 1
+    dev = torch.device(device) if isinstance(device, str) else torch.device("cuda", device)
+    cidx = torch.as_tensor(d["county_idx"], device=dev, dtype=torch.long)
+    floor = torch.as_tensor(d["floor"], device=dev, dtype=torch.float64)
+    y = torch.as_tensor(d["log_radon"], device=dev, dtype=torch.float64)
+    norm = _lkj_log_norm(float(eta), 2)
+    half_log_2pi = 0.5 * math.log(2 * math.pi)
+
+    def halfnormal(v, s):
+        return 0.5 * math.log(2 / math.pi) - math.log(s) - 0.5 * (v / s) ** 2
+
+    def logp(x):
+        intercept, fe, lsig = x[:, 0], x[:, 1], x[:, 2]
+        p0, p1, p2 = x[:, 3], x[:, 4], x[:, 5]
+        ab = x[:, 6:].reshape(-1, 2, n)
+        sig = lsig.exp()
+        l00, l10, l11 = p0.exp(), p1, p2.exp()
+        sd0, sd1 = l00, torch.sqrt(l10 * l10 + l11 * l11)
+        # LKJCholeskyCov: LKJ on the correlation factor, HalfNormal(1) standard deviations, Jacobians (sd scaling, log diagonal)
+        lcd1 = torch.log(l11 / sd1)
+        lp = norm + (2 * eta - 2) * lcd1 + lcd1 - torch.log(sd1) + halfnormal(sd0, 1.0) + halfnormal(sd1, 1.0) + p0 + p2
+        lp = lp - 0.5 * (intercept / 10.0) ** 2 - math.log(10.0) - half_log_2pi - 0.5 * (fe / 2.0) ** 2 - math.log(2.0) - half_log_2pi
+        lp = lp + halfnormal(sig, 1.5) + lsig
+        zero = torch.zeros_like(l00)
+        Lm = torch.stack([torch.stack([l00, zero], -1), torch.stack([l10, l11], -1)], -2)
+        lp = lp + MultivariateNormal(torch.zeros(2, dtype=torch.float64, device=dev), scale_tril=Lm[:, None], validate_args=False).log_prob(
+            ab.transpose(1, 2)).sum(-1)
+        mu = intercept[:, None] + ab[:, 0, cidx] + floor * (fe[:, None] + ab[:, 1, cidx])
+        r = (y - mu) / sig[:, None]
+        lp = lp - 0.5 * (r * r).sum(-1) - y.shape[0] * (lsig + half_log_2pi)
+        return lp
+
+    return 6 + 2 * n, logp

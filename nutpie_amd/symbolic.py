@@ -21,6 +21,12 @@ schedules logp and gradient together into wave-wide loops — one wavefront eval
 the elements of a *dimension* (a coordinate of the model: counties, observations) —, and prints the HIP device function
 ``nphip_density`` that :func:`nutpie_amd.from_density_source` compiles into the engine's resident NUTS kernel.
 
+Per-chain dense matrices (K x K, K <= 32, row-major on a ``Model.product``): ``cholesky(A)``, ``solve_lower(L, B)`` (B K x N: every
+column a right-hand side), ``log_det_chol(L)``, ``mvnormal_lpdf(value, mu, cov=... | chol=...)`` (value K x N: every column one draw),
+``lkj_corr_cholesky_lpdf(L, eta)`` and ``m.lkj_cholesky_cov(name, n, eta, sd_lpdf)`` (PyMC's ``LKJCholeskyCov``: packed factor with a
+log-transformed diagonal) — each matrix operation a stage between loops that one device routine runs (``csrc/chain_linalg.h``,
+DESIGN.md §11.5); such models run with one wave per chain.
+
 Also: ``m.matrix("X", values, dim="obs", cols="coef")`` and ``X @ beta`` (a design matrix: lowered to a sum over its columns, the
 transposed product to one wave-wide sum per column); ``lower=`` / ``upper=`` / both (log and logit-interval transforms with their
 Jacobians); densities ``normal``, ``halfnormal``, ``student_t``, ``cauchy``, ``halfcauchy``, ``exponential``, ``lognormal``, ``gamma``,
@@ -55,7 +61,8 @@ __all__ = ["Model", "Expr", "Matrix", "exp", "log", "log1p", "sqrt", "softplus",
            "absolute", "sign", "select", "pad", "trunc", "where_lt", "elem", "stack", "normal_lpdf",
            "halfnormal_lpdf", "student_t_lpdf", "cauchy_lpdf", "halfcauchy_lpdf", "exponential_lpdf", "lognormal_lpdf", "gamma_lpdf",
            "inverse_gamma_lpdf", "beta_lpdf", "laplace_lpdf", "logistic_lpdf", "weibull_lpdf", "uniform_lpdf",
-           "bernoulli_logit_lpmf", "binomial_logit_lpmf", "negative_binomial_log_lpmf", "poisson_log_lpmf", "dirichlet_lpdf", "flat_lpdf"]
+           "bernoulli_logit_lpmf", "binomial_logit_lpmf", "negative_binomial_log_lpmf", "poisson_log_lpmf", "dirichlet_lpdf", "flat_lpdf",
+           "cholesky", "solve_lower", "log_det_chol", "mvnormal_lpdf", "lkj_corr_cholesky_lpdf"]
 
 _WAVE = 64
 _SEG_BATCH = os.environ.get("NUTPIE_AMD_SEG_MODE", "select") != "loop"   # (developer switch: "loop" = plain loops over a segment)
@@ -427,6 +434,89 @@ def elem(v: Expr, c: int) -> Expr:
     return Expr("elem", (v,), None, int(c))
 
 
+# --------------------------------------------------------------------------- one chain's dense matrices
+# Matrix stages: K x K (K <= 32) and K x N values, row-major on a fixed-size dimension (a ``Model.product``), that one device routine
+# (csrc/chain_linalg.h) turns into another between two loops.  ``chol`` / ``trsv`` are the user's; the other three are the adjoints
+# the gradient emits.  payload = (K, N): N the columns of the right-hand sides (K for the K x K stages).
+_MATOPS = ("chol", "trsv", "trsv_t", "trsv_gl", "chol_adj")
+MAX_MATRIX = 32     # the largest K a compiled density factors (8 KB per matrix and chain)
+
+
+def _side(e: Expr, what: str) -> int:
+    if e.dim is None or e.dim.size is None:
+        raise ValueError(f"{what}: a matrix lives on a fixed-size dimension (Model.product(rows, cols))")
+    k = int(round(math.sqrt(e.dim.size)))
+    if k * k != e.dim.size:
+        raise ValueError(f"{what}: a square matrix has K * K elements, dimension {e.dim.name!r} has {e.dim.size}")
+    return k
+
+
+def cholesky(A) -> Expr:
+    """``L`` with ``L L^T = A`` (K x K, row-major; the upper triangle of ``L`` is zero).  Only the lower triangle of ``A`` is read,
+    as by ``torch.linalg.cholesky``, and the gradient is that of what is read: an ``A`` filled below the diagonal only is as valid as a
+    symmetric one (for a symmetric ``A`` the parameter gradient is torch.autograd's).  A matrix that is not positive definite gives
+    NaN everywhere (the log-density is NaN there: an impossible point)."""
+    A = Expr.wrap(A)
+    k = _side(A, "cholesky")
+    return Expr("chol", (A,), A.dim, (k, k))
+
+
+def solve_lower(L, B) -> Expr:
+    """``L^-1 B`` for a lower-triangular K x K ``L`` (its upper triangle is not read) and a K x N ``B`` (row-major: element
+    (i, n) at ``i N + n``, every COLUMN a right-hand side — a value on ``Model.product(k, n)``).  The result lives where ``B`` does."""
+    L, B = Expr.wrap(L), Expr.wrap(B)
+    k = _side(L, "solve_lower")
+    if B.dim is None or B.dim.size is None or B.dim.size % k:
+        raise ValueError(f"solve_lower: the right-hand sides are a K x N value on a fixed-size dimension (K = {k})")
+    return Expr("trsv", (L, B), B.dim, (k, B.dim.size // k))
+
+
+def log_det_chol(L) -> Expr:
+    """``sum(log(diag(L)))``: half the log-determinant of ``L L^T``."""
+    k = _side(L, "log_det_chol")
+    total = None
+    for i in range(k):
+        t = log(elem(L, i * k + i))
+        total = t if total is None else total + t
+    return total
+
+
+def mvnormal_lpdf(value, mu, *, cov=None, chol=None) -> Expr:
+    """Sum over the N columns of the K x N ``value`` (element (i, n) at ``i N + n``: ``Model.product(k, n)``, every column one
+    draw) of the multivariate normal log-density with mean ``mu`` (a scalar or a value on the same dimension: ``Model.broadcast``)
+    and covariance ``cov`` (K x K) or its lower Cholesky factor ``chol``."""
+    if (cov is None) == (chol is None):
+        raise ValueError("mvnormal_lpdf: give cov= or chol=")
+    value, mu = Expr.wrap(value), Expr.wrap(mu)
+    L = cholesky(cov) if chol is None else Expr.wrap(chol)
+    k = _side(L, "mvnormal_lpdf")
+    if value.dim is None or value.dim.size is None or value.dim.size % k:
+        raise ValueError(f"mvnormal_lpdf: value is a K x N value on a fixed-size dimension (K = {k})")
+    n = value.dim.size // k
+    z = solve_lower(L, value - mu)
+    return -0.5 * (z * z).sum() - n * log_det_chol(L) - (n * k) * _HALF_LOG_2PI
+
+
+def _lkj_log_norm(eta: float, k: int) -> float:
+    """log of the LKJ(eta) normalising constant of K x K correlation matrices (Lewandowski, Kurowicka & Joe 2009, eq. 16)"""
+    c = 0.0
+    for i in range(1, k):
+        b = eta + (k - i - 1) / 2.0
+        c += (2.0 * eta - 2.0 + k - i) * (k - i) * math.log(2.0) + (k - i) * (2.0 * math.lgamma(b) - math.lgamma(2.0 * b))
+    return -c
+
+
+def lkj_corr_cholesky_lpdf(L, eta: float) -> Expr:
+    """Log-density of the Cholesky factor ``L`` (K x K) of an LKJ(``eta``) correlation matrix, with respect to its strictly lower
+    elements (Stan's ``lkj_corr_cholesky``): ``sum_{i >= 1} (K - i - 1 + 2 eta - 2) log L[i][i]`` + the normalising constant."""
+    L = Expr.wrap(L)
+    k = _side(L, "lkj_corr_cholesky_lpdf")
+    total = Expr.const(_lkj_log_norm(float(eta), k))
+    for i in range(1, k):
+        total = total + (k - i - 1 + 2.0 * float(eta) - 2.0) * log(elem(L, i * k + i))
+    return total
+
+
 def stack(scalars, dim: Dim) -> Expr:
     """The vector on ``dim`` whose elements are the given scalars."""
     scalars = [Expr.wrap(v) for v in scalars]
@@ -728,6 +818,14 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
             acc(a, _segsum(g, n.payload))
         elif n.op == "segsum":
             acc(a, _bcast(g, n.payload.into)[n.payload])
+        elif n.op == "chol":
+            acc(a, Expr("chol_adj", (n, _bcast(g, d)), a.dim, n.payload))
+        elif n.op == "trsv":
+            gb = Expr("trsv_t", (a, _bcast(g, d)), b.dim, n.payload)      # B-bar = L^-T X-bar
+            acc(b, gb)
+            acc(a, Expr("trsv_gl", (gb, n), a.dim, n.payload))            # L-bar = -tril(B-bar X^T)
+        elif n.op in _MATOPS:
+            raise NotImplementedError("second derivatives of the matrix stages")
         else:
             raise AssertionError(n.op)
     return [adj.get(w.id, Expr.const(0.0)) for w in wrt]
@@ -743,6 +841,60 @@ def _np_unary(op: str, a: np.ndarray) -> np.ndarray:
 
         return {"erf": sp.erf, "erfc": sp.erfc, "lgamma": sp.gammaln, "digamma": sp.digamma}[op](a)
     return {"tanh": np.tanh, "expm1": np.expm1, "sin": np.sin, "cos": np.cos, "atan": np.arctan, "abs": np.abs, "sign": np.sign}[op](a)
+
+
+def _np_chol(a: np.ndarray) -> np.ndarray:
+    """[N, K, K] -> the lower Cholesky factors (lower triangles read; column by column as csrc/chain_linalg.h), NaN where a pivot fails"""
+    N, K, _ = a.shape
+    L = np.zeros_like(a)
+    bad = np.zeros(N, dtype=bool)
+    for j in range(K):
+        s = a[:, j:, j] - np.einsum("nik,nk->ni", L[:, j:, :j], L[:, j, :j])
+        d = s[:, 0]
+        ok = (d > 0.0) & np.isfinite(d)
+        bad |= ~ok
+        r = np.sqrt(np.where(ok, d, 1.0))
+        L[:, j, j] = r
+        L[:, j + 1:, j] = s[:, 1:] / r[:, None]
+    L[bad] = np.nan
+    return L
+
+
+def _np_solve_lower(L: np.ndarray, B: np.ndarray) -> np.ndarray:
+    """L^-1 B: L [N, K, K] (lower triangle read), B [N, K, M]"""
+    X = np.zeros(B.shape)
+    for i in range(L.shape[1]):
+        X[:, i] = (B[:, i] - np.einsum("nk,nkm->nm", L[:, i, :i], X[:, :i])) / L[:, i, i][:, None]
+    return X
+
+
+def _np_solve_lower_t(L: np.ndarray, G: np.ndarray) -> np.ndarray:
+    """L^-T G"""
+    Y = np.zeros(G.shape)
+    for i in reversed(range(L.shape[1])):
+        Y[:, i] = (G[:, i] - np.einsum("nk,nkm->nm", L[:, i + 1:, i], Y[:, i + 1:])) / L[:, i, i][:, None]
+    return Y
+
+
+def _np_matop(op: str, args: list[np.ndarray], k: int, m: int) -> np.ndarray:
+    N = args[0].shape[0]
+    mats = [v.reshape(N, k, -1) for v in args]
+    if op == "chol":
+        out = _np_chol(mats[0])
+    elif op == "trsv":
+        out = _np_solve_lower(mats[0], mats[1])
+    elif op == "trsv_t":
+        out = _np_solve_lower_t(mats[0], mats[1])
+    elif op == "trsv_gl":
+        out = -np.tril(np.einsum("nim,njm->nij", mats[0], mats[1]))
+    else:   # chol_adj: G = L^-T P L^-1, P = Phi(L^T tril(L-bar)) symmetrised (torch.autograd's G), folded onto the lower triangle
+        L, Lb = mats
+        M = np.tril(np.einsum("nki,nkj->nij", L, np.tril(Lb)))
+        P = 0.5 * (M + np.transpose(np.tril(M, -1), (0, 2, 1)))
+        Y = _np_solve_lower_t(L, P)
+        G = np.transpose(_np_solve_lower_t(L, np.transpose(Y, (0, 2, 1))), (0, 2, 1))
+        out = np.tril(G) + np.tril(np.transpose(G, (0, 2, 1)), -1)
+    return out.reshape(N, -1)
 
 
 def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.ndarray]:
@@ -833,6 +985,9 @@ def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.
                 idx = np.asarray(data[n.payload.name], dtype=np.int64)
                 v = np.zeros((N, dim_len(n.dim)))
                 np.add.at(v, (slice(None), idx), a)
+            elif n.op in _MATOPS:
+                args = [np.broadcast_to(val[x_.id][:, None] if val[x_.id].ndim == 1 else val[x_.id], (N, dim_len(x_.dim))) for x_ in n.args]
+                v = _np_matop(n.op, args, *n.payload)
             else:
                 raise AssertionError(n.op)
         val[n.id] = np.asarray(v, dtype=np.float64)
@@ -879,7 +1034,7 @@ class _Gen:
         self.level: dict[int, int] = {}
         for n in self.order:
             lv = max([self.level[a.id] for a in n.args], default=0)
-            if n.op in ("sum", "max", "gather", "segsum") or (n.op in ("elem", "pad", "trunc") and n.args[0].op not in ("vparam", "data")):
+            if n.op in ("sum", "max", "gather", "segsum") + _MATOPS or (n.op in ("elem", "pad", "trunc") and n.args[0].op not in ("vparam", "data")):
                 lv += 1
             self.level[n.id] = lv
         # what lives in per-chain LDS: sources of gathers (unless they are parameters or data, read in place), arguments of
@@ -894,6 +1049,15 @@ class _Gen:
                 self.stored[n.args[0].id] = ("plain", n.args[0].dim)     # a scalar read of one element of a computed vector
             elif n.op == "stack":
                 self.stored[n.id] = ("scalars", n.dim)                   # written by the scalar code, element by element
+        # matrix stages: their operands are stored by the loops that produce them, their results by the device routine
+        for n in self.order:
+            if n.op in _MATOPS:
+                for a in n.args:
+                    if self.stored.get(a.id, ("plain",))[0] == "plain":
+                        self.stored[a.id] = ("plain", a.dim)
+        for n in self.order:
+            if n.op in _MATOPS:
+                self.stored[n.id] = ("matop", n.dim)
         # ... and segment sums that more than one loop needs.  Element-wise values are recomputed in every loop that needs them
         # (a few operations on values that are read anyway); a segment sum is an inner loop over its range.
         evaluated: dict[int, set[int]] = {}     # segment sum -> the levels of the loops that evaluate it
@@ -906,7 +1070,7 @@ class _Gen:
                 if n.dim is None or n.id in seen:
                     continue
                 seen.add(n.id)
-                if n.op == "stack" or (n.id in self.stored and self.level[n.id] < lv[1]):
+                if n.op == "stack" or n.op in _MATOPS or (n.id in self.stored and self.level[n.id] < lv[1]):
                     continue               # read from LDS
                 if n.op == "segsum":
                     evaluated.setdefault(n.id, set()).add(lv[1])
@@ -932,7 +1096,7 @@ class _Gen:
                 seen.add(n.id)
                 if n.op == "vparam":
                     reads.setdefault(n.id, set()).add(key)
-                if n.op in ("stack", "gather", "segsum", "pad", "trunc") or (n.id in self.stored and self.level[n.id] < key[1]):
+                if n.op in ("stack", "gather", "segsum", "pad", "trunc") + _MATOPS or (n.id in self.stored and self.level[n.id] < key[1]):
                     continue
                 stack.extend(n.args)
         for nid, loops in reads.items():
@@ -949,7 +1113,7 @@ class _Gen:
                 a = n.args[0]
                 roots.setdefault((id(a.dim), self.level[a.id]), []).append(a)
         for key, (how, _) in self.stored.items():
-            if how == "scalars":
+            if how in ("scalars", "matop"):
                 continue
             node = by_id[key[1] if isinstance(key, tuple) else key]
             roots.setdefault((id(node.dim), self.level[node.id]), []).append(node)
@@ -971,6 +1135,8 @@ class _Gen:
             emit(stage_src)
         if any(n.op == "digamma" for n in self.order):
             emit(_DIGAMMA_SOURCE)
+        if any(n.op in _MATOPS for n in self.order):
+            emit('#include "chain_linalg.h"')
         emit(f"__device__ double {self.fn_name}(const NphipData& data, int dim, const double* x, double* g, double* lds, const double* shared, int lane) {{")
         # dimension lengths, data pointers (shared LDS where staged, else global), LDS scratch
         for d in m._dims.values():
@@ -1044,13 +1210,16 @@ class _Gen:
                         emit(f"        {self.store_name[n.id]}[{c}] = {self.sref(a_)};")
                 emit("    }")
                 emit("    nphip_chain_barrier();")
+            for n in self.order:
+                if n.op in _MATOPS and self.level[n.id] == lv:
+                    emit(self.matop_call(n))
             mark(f"scalars of level {lv}")
             # loops of this level, one per dimension that has something to produce here
             for d in m._dims.values():
                 sums = [n for n in self.order if n.op in ("sum", "max") and n.args[0].dim is d and self.level[n.args[0].id] == lv]
                 stores = []
                 for key, (how, sd) in self.stored.items():
-                    if sd is not d or how == "scalars":
+                    if sd is not d or how in ("scalars", "matop"):
                         continue
                     node_id = key[1] if isinstance(key, tuple) else key
                     if self.level[node_id] == lv:
@@ -1079,6 +1248,15 @@ class _Gen:
             emit(f"    return {self.sref(self.logp)};")
         emit("}")
         return "\n".join(L), shared_fields
+
+    # ---- matrix stages (csrc/chain_linalg.h; every routine ends with the wave's barrier)
+    def matop_call(self, n: Expr) -> str:
+        k, m = n.payload
+        args = ", ".join(self.store_name[a.id] for a in n.args)
+        out = self.store_name[n.id]
+        fn = {"chol": f"cholesky<{k}>", "trsv": f"solve_lower<{k}, {m}>", "trsv_t": f"solve_lower_t<{k}, {m}, {m}, 1>",
+              "trsv_gl": f"solve_lower_adj_l<{k}, {m}>", "chol_adj": f"cholesky_adj<{k}>"}[n.op]
+        return f"    nphip_la::{fn}({args}, {out}, lane);"
 
     # ---- scalars
     def sref(self, n: Expr) -> str:
@@ -1148,7 +1326,7 @@ class _Gen:
                 elif n.op == "datacol":
                     mname, c, K = n.payload
                     stages[0].append(f"        const double {name} = D_{mname}[j_{u} * {K} + {c}];")
-                elif n.op == "stack":
+                elif n.op == "stack" or n.op in _MATOPS:
                     stages[0].append(f"        const double {name} = {self.store_name[n.id]}[j_{u}];")
                 elif n.op == "gather":
                     src, index = n.args[0], n.payload
@@ -1555,6 +1733,36 @@ class Model:
         self._det.append((name, value))
         return value
 
+    def lkj_cholesky_cov(self, name: str, n: int, eta: float, sd_lpdf) -> tuple[Expr, Expr]:
+        """PyMC's ``LKJCholeskyCov(name, n=n, eta=eta, sd_dist=...)``: the Cholesky factor of an n x n covariance, a parameter stored as
+        its packed lower triangle (row by row; ``name`` + ``_cholesky-cov-packed__``: the diagonal log-transformed), with the LKJ(eta)
+        density of the implied correlation, ``sd_lpdf(sd)`` (an expression of one standard deviation) on every standard deviation, the
+        Jacobian of (packed factor -> standard deviations, correlation factor) and that of the log transform.  Returns ``(L, sd)``: L on
+        ``product(name + "_k", name + "_k")`` (row-major, zero above the diagonal) and the standard deviations on ``name + "_k"``."""
+        k = int(n)
+        kd = self.dim(name + "_k", k)
+        raw = self.param(name + "_cholesky-cov-packed__", dim=name + "_packed", size=k * (k + 1) // 2)
+        ent, jac = {}, None
+        for i in range(k):
+            for j in range(i + 1):
+                r = elem(raw, i * (i + 1) // 2 + j)
+                ent[(i, j)] = exp(r) if i == j else r
+                if i == j:
+                    jac = r if jac is None else jac + r
+        sds, lp = [], Expr.const(_lkj_log_norm(float(eta), k))
+        for i in range(k):
+            ss = None
+            for j in range(i + 1):
+                ss = ent[(i, j)] * ent[(i, j)] if ss is None else ss + ent[(i, j)] * ent[(i, j)]
+            sd = sqrt(ss)
+            sds.append(sd)
+            log_cd = log(ent[(i, i)]) - log(sd)          # log of the correlation factor's diagonal element
+            lp = lp + (2.0 * float(eta) - 3.0 + k - i) * log_cd + log_cd - i * log(sd) + Expr.wrap(sd_lpdf(sd))
+        self._terms.append(lp + jac)
+        prod = self.product(kd.name, kd.name)
+        L = stack([ent.get((i, j), Expr.const(0.0)) for i in range(k) for j in range(k)], prod)
+        return L, stack(sds, kd)
+
     def data(self, name: str, values, dim: str | None = None) -> Expr:
         """Observed / shared data: a float array over ``dim`` or (``dim=None``) one float.  ``with_data`` can replace it."""
         self._check_new_data(name)
@@ -1841,6 +2049,15 @@ class Model:
             self._det = [(n, e) for n, e in self._det if n in wanted or n in free]
         logp = self.logp_expr()
         grads = gradient(logp, self._params)
+        mats = [n for n in _topo([logp] + grads + [e for _, e in self._det]) if n.op in _MATOPS]
+        if mats:
+            # one wavefront per chain runs the matrix stages (csrc/chain_linalg.h)
+            k = max(n.payload[0] for n in mats)
+            if k > MAX_MATRIX:
+                raise ValueError(f"a compiled density factors matrices of up to {MAX_MATRIX} x {MAX_MATRIX} (this model: {k} x {k})")
+            if waves_per_chain not in (None, 1):
+                raise ValueError("a model with matrix stages (cholesky / solve_lower) runs with waves_per_chain=1")
+            waves_per_chain = 1
         self._staged = 8 * self._shared_doubles_unconditional(self._data) <= self.STAGE_LIMIT
         if waves_per_chain is None:
             for waves_per_chain in (1, 2, 4):

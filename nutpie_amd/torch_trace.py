@@ -540,6 +540,47 @@ def _pow_traced(x: Expr, y: Expr) -> Expr:
     return S.exp(y * S.log(x))
 
 
+def _matrix(it: _Interp, v, what: str) -> tuple[_Sym, int]:
+    """a traced square matrix (leading axes of length one) as a K x K value on its own dimension"""
+    v = it.sym(v)
+    if len(v.shape) < 2 or v.shape[-1] != v.shape[-2] or _numel(v.shape) != v.shape[-1] ** 2:
+        raise UnsupportedTorchOp(f"{what} of a traced matrix of shape {v.shape} (one K x K matrix per chain)")
+    k = v.shape[-1]
+    return _Sym(S._bcast(v.expr, it.dim(k * k)), v.shape), k
+
+
+def _cholesky(it: _Interp, a) -> _Sym:
+    A, k = _matrix(it, a, "cholesky")
+    if k > S.MAX_MATRIX:
+        raise UnsupportedTorchOp(f"cholesky of a {k} x {k} traced matrix (compiled densities factor up to {S.MAX_MATRIX} x {S.MAX_MATRIX})")
+    return _Sym(S.cholesky(A.expr), A.shape)
+
+
+def _solve_triangular(it: _Interp, a, b, upper: bool, left: bool) -> _Sym:
+    """A X = B (``left``) or X A = B with a traced triangular A, as ``solve_lower`` of K x N right-hand sides"""
+    if not left:        # X A = B  <=>  A^T X^T = B^T
+        bt = it.move(it.sym(b), lambda t: t.transpose(-1, -2))
+        at = it.move(it.sym(a), lambda t: t.transpose(-1, -2))
+        return it.move(_solve_triangular(it, at, bt, not upper, True), lambda t: t.transpose(-1, -2))
+    if upper:           # U^-1 B = R (R U R)^-1 R B with R the reversal: R U R is lower triangular
+        ar = it.move(it.sym(a), lambda t: t.flip(-1, -2))
+        br = it.move(it.sym(b), lambda t: t.flip(-2))
+        return it.move(_solve_triangular(it, ar, br, False, True), lambda t: t.flip(-2))
+    A, k = _matrix(it, a, "solve_triangular")
+    if k > S.MAX_MATRIX:
+        raise UnsupportedTorchOp(f"solve_triangular with a {k} x {k} traced matrix (compiled densities solve up to {S.MAX_MATRIX} x {S.MAX_MATRIX})")
+    B = it.sym(b)
+    if len(B.shape) < 2 or B.shape[-2] != k:
+        raise UnsupportedTorchOp(f"solve_triangular: right-hand sides of shape {B.shape} for a {k} x {k} matrix")
+    bshape = B.shape
+    batch, n = bshape[:-2], bshape[-1]
+    m = _numel(batch) * n
+    # the right-hand sides as K x (batch, N): every column one of them
+    Bk = it.move(B, lambda t: t.movedim(-2, 0).reshape(k, m))
+    X = _Sym(S.solve_lower(A.expr, S._bcast(Bk.expr, it.dim(k * m))), (k, m))
+    return it.move(X, lambda t: t.reshape(k, *batch, n).movedim(0, -2))
+
+
 def _scalar(v) -> float:
     if hasattr(v, "item"):
         return float(v.item())
@@ -901,11 +942,25 @@ def _run(gm, it: _Interp, x_shape, data_values: dict[str, Any]):
                 env[node] = _Sym(S._segsum(pairs, it.index(dst, dst.size, n_)), shp)
         elif base == "dot" or base == "vdot":
             env[node] = it.sum(B(args[0], args[1], lambda x, y: x * y))
+        elif base in ("linalg_cholesky_ex", "linalg_cholesky", "cholesky"):
+            # a traced matrix: the IR's Cholesky stage (one chain's K x K matrix; csrc/chain_linalg.h)
+            upper = bool(args[1] if len(args) > 1 else kwargs.get("upper", False))
+            Lsym = _cholesky(it, a0)
+            if upper:
+                Lsym = it.move(Lsym, lambda t: t.transpose(-1, -2))
+            if base == "linalg_cholesky_ex":
+                # (info: 0 — a matrix that is not positive definite makes the density NaN instead of raising)
+                env[node] = (Lsym, torch.zeros(Lsym.shape[:-2], dtype=torch.int32))
+            else:
+                env[node] = Lsym
+        elif base == "linalg_solve_triangular" and not it.is_const(args[0]):
+            # a traced triangular matrix: the IR's triangular solve (lower, left) — other forms through transposes and reversals
+            if bool(kwargs.get("unitriangular", False)):
+                raise UnsupportedTorchOp(f"{name} with unitriangular=True and a traced matrix")
+            env[node] = _solve_triangular(it, args[0], args[1], bool(kwargs.get("upper", False)), bool(kwargs.get("left", True)))
         elif base == "linalg_solve_triangular":
             # A X = B (left) or X A = B with a CONSTANT triangular A (the scale_tril of a MultivariateNormal): a product with A^-1
             A_, B_ = args[0], args[1]
-            if not it.is_const(A_):
-                raise UnsupportedTorchOp(f"{name} with a traced matrix (a covariance that depends on parameters)")
             eye = torch.eye(A_.shape[-1], dtype=A_.dtype)
             Ainv = torch.linalg.solve_triangular(A_, eye.expand_as(A_).contiguous(), upper=bool(kwargs.get("upper", False)),
                                                  left=True, unitriangular=bool(kwargs.get("unitriangular", False)))
