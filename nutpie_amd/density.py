@@ -193,6 +193,8 @@ def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verb
     deps = [os.path.join(_CSRC, f) for f in ("kernels.hip", "engine_types.h", "dense_tile.h")] + [os.path.join(_INCLUDE, "nphip_spec.h")]
     if '#include "chain_linalg.h"' in user_source:
         deps.append(os.path.join(_CSRC, "chain_linalg.h"))
+    if '#include "chain_scan.h"' in user_source:
+        deps.append(os.path.join(_CSRC, "chain_scan.h"))
     h = hashlib.sha256()
     h.update(src.encode())
     for d in deps:

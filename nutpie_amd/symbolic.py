@@ -27,6 +27,12 @@ column a right-hand side), ``log_det_chol(L)``, ``mvnormal_lpdf(value, mu, cov=.
 log-transformed diagonal) — each matrix operation a stage between loops that one device routine runs (``csrc/chain_linalg.h``,
 DESIGN.md §11.5); such models run with one wave per chain.
 
+First-order linear recurrences (scans): ``linear_recurrence(a, b, init=0.0, along=None)`` is x_t = a_t x_{t-1} + b_t with x_{-1} =
+``init`` (``a`` a scalar or a value on ``b``'s dimension; ``along`` the time axis of a ``Model.product(rows, time)``: every row its own
+recurrence, ``init`` a scalar or a value on ``rows``), ``cumsum(x, along=None)`` the prefix sum (a = 1): a random walk, an AR(1) latent
+path, a GARCH(1, 1) variance or an exponential-smoothing level — a stage between loops that one device routine runs on the chain's
+wave(s) (``csrc/chain_scan.h``), up to four waves per chain.
+
 Also: ``m.matrix("X", values, dim="obs", cols="coef")`` and ``X @ beta`` (a design matrix: lowered to a sum over its columns, the
 transposed product to one wave-wide sum per column); ``lower=`` / ``upper=`` / both (log and logit-interval transforms with their
 Jacobians); densities ``normal``, ``halfnormal``, ``student_t``, ``cauchy``, ``halfcauchy``, ``exponential``, ``lognormal``, ``gamma``,
@@ -62,7 +68,8 @@ __all__ = ["Model", "Expr", "Matrix", "exp", "log", "log1p", "sqrt", "softplus",
            "halfnormal_lpdf", "student_t_lpdf", "cauchy_lpdf", "halfcauchy_lpdf", "exponential_lpdf", "lognormal_lpdf", "gamma_lpdf",
            "inverse_gamma_lpdf", "beta_lpdf", "laplace_lpdf", "logistic_lpdf", "weibull_lpdf", "uniform_lpdf",
            "bernoulli_logit_lpmf", "binomial_logit_lpmf", "negative_binomial_log_lpmf", "poisson_log_lpmf", "dirichlet_lpdf", "flat_lpdf",
-           "cholesky", "solve_lower", "log_det_chol", "mvnormal_lpdf", "lkj_corr_cholesky_lpdf"]
+           "cholesky", "solve_lower", "log_det_chol", "mvnormal_lpdf", "lkj_corr_cholesky_lpdf",
+           "linear_recurrence", "cumsum"]
 
 _WAVE = 64
 _SEG_BATCH = os.environ.get("NUTPIE_AMD_SEG_MODE", "select") != "loop"   # (developer switch: "loop" = plain loops over a segment)
@@ -78,6 +85,9 @@ class Dim:
         self.size = size                  # int, or None for a data dimension whose length comes from the data block
         self.runtime_len = runtime_len    # the data array whose length is the dimension's (times runtime_div: a matrix's rows)
         self.runtime_div = runtime_div
+        self.factors: tuple[Dim, Dim] | None = None   # (rows, cols) of a Model.product
+        self._model = None                # (weak) the Model that declared it: where a scan's gradient registers its shifted read
+        self._scan_aux: dict[int, tuple] = {}   # row length T -> (index of element t - 1, "first element of a row" data or None)
 
     def len_c(self) -> str:
         if self.size is not None:
@@ -517,6 +527,85 @@ def lkj_corr_cholesky_lpdf(L, eta: float) -> Expr:
     return total
 
 
+# --------------------------------------------------------------------------- first-order linear recurrences
+# Scan stages: x_t = a_t x_{t-1} + b_t over R rows of T elements, row-major on a fixed-size dimension, that one device routine
+# (csrc/chain_scan.h) runs between two loops.  ``scan`` (args a, b, init) is the user's; ``rscan`` (args a, xbar) the adjoint the
+# gradient emits: lambda_t = a_{t+1} lambda_{t+1} + xbar_t, lambda_{T-1} = xbar_{T-1}.  ``a`` is a value on the dimension, a scalar, or
+# the constant 1 (a prefix sum); ``init`` a scalar or a value on the rows.  payload = (R, T).
+_SCANOPS = ("scan", "rscan")
+_STAGES = _MATOPS + _SCANOPS
+
+
+def _scan(a, b, init, R: int, T: int, rows: Dim | None = None) -> Expr:
+    a, b, init = Expr.wrap(a), Expr.wrap(b), Expr.wrap(init)
+    d = b.dim
+    if d is None or d.size is None or d.size != R * T:
+        raise ValueError("linear_recurrence: b is a value on a fixed-size dimension (R rows of T elements)")
+    if a.dim is not None and a.dim is not d:
+        raise ValueError("linear_recurrence: a is a scalar or a value on the dimension of b")
+    if init.dim is not None and (rows is None or init.dim is not rows):
+        raise ValueError("linear_recurrence: init is a scalar or a value on the rows of b")
+    if not (a.op == "const" and init.op == "const"):
+        # the gradient with respect to a or init reads x_{t-1}: a constant gather, registered with the model now
+        m = d._model() if d._model is not None else None
+        if m is None:
+            raise ValueError("linear_recurrence: b lives on a dimension of no Model")
+        m._scan_aux(d, R, T, rows if init.dim is not None else None)
+    return Expr("scan", (a, b, init), d, (int(R), int(T)))
+
+
+def linear_recurrence(a, b, init=0.0, along: str | None = None) -> Expr:
+    """``x_t = a_t x_{t-1} + b_t`` with ``x_{-1} = init``, along a dimension of fixed size.  ``b``: a value on it; ``a``: a scalar
+    expression or a value on the same dimension.  ``along``: the time axis of a ``Model.product(rows, time)`` — every row is its own
+    recurrence and ``init`` a scalar or a value on ``rows``; time must be the inner (second) axis.  Without ``along`` the whole
+    dimension is one series.  A non-finite ``a`` or ``b`` makes the values that depend on it non-finite; ``|a| > 1`` grows
+    geometrically and overflows on long series (not guarded)."""
+    b = Expr.wrap(b)
+    d = b.dim
+    if d is None or d.size is None:
+        raise ValueError("linear_recurrence: b is a value on a dimension of fixed size")
+    if along is None or (d.factors is None and along == d.name):
+        return _scan(a, b, init, 1, d.size)
+    if d.factors is None:
+        raise ValueError(f"linear_recurrence: along={along!r} names no axis of dimension {d.name!r}")
+    rows, time = d.factors
+    if along == rows.name and along != time.name:
+        raise ValueError(f"linear_recurrence: {along!r} is the outer axis of {d.name!r}; the time axis must be the inner (second) one")
+    if along != time.name:
+        raise ValueError(f"linear_recurrence: along={along!r} names no axis of dimension {d.name!r}")
+    return _scan(a, b, init, rows.size, time.size, rows)
+
+
+def cumsum(x, along: str | None = None) -> Expr:
+    """The prefix sum of ``x`` (``linear_recurrence(1.0, x, along=along)``)."""
+    return linear_recurrence(1.0, x, 0.0, along)
+
+
+def _scan_grads(n: Expr, lam: Expr) -> tuple[Expr | None, Expr | None]:
+    """adjoints of ``a`` and ``init`` in x = scan(a, b, init), lam the adjoint of b: a-bar_t = lam_t x_{t-1} (x_{-1} = init),
+    init-bar = a_0 lam_0 per row"""
+    a, _, init = n.args
+    R, T = n.payload
+    d = n.dim
+    if a.op == "const" and init.op == "const":
+        return None, None
+    prev, first, to_r = d._scan_aux[T]
+
+    def at_first(v, w):     # v on the first element of every row, w on the others
+        return where_lt(d, 1, v, w) if R == 1 else select(first, v, w)
+
+    ga = gi = None
+    if a.op != "const":
+        ga = lam * at_first(init if init.dim is None else init[to_r], n[prev])
+    if init.op != "const":
+        if R == 1 and init.dim is None:
+            gi = (a if a.dim is None else elem(a, 0)) * elem(lam, 0)
+        else:
+            first_terms = at_first(a * lam, 0.0)
+            gi = first_terms.sum() if init.dim is None else _segsum(first_terms, to_r)
+    return ga, gi
+
+
 def stack(scalars, dim: Dim) -> Expr:
     """The vector on ``dim`` whose elements are the given scalars."""
     scalars = [Expr.wrap(v) for v in scalars]
@@ -824,8 +913,16 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
             gb = Expr("trsv_t", (a, _bcast(g, d)), b.dim, n.payload)      # B-bar = L^-T X-bar
             acc(b, gb)
             acc(a, Expr("trsv_gl", (gb, n), a.dim, n.payload))            # L-bar = -tril(B-bar X^T)
-        elif n.op in _MATOPS:
-            raise NotImplementedError("second derivatives of the matrix stages")
+        elif n.op == "scan":
+            lam = Expr("rscan", (a, _bcast(g, d)), d, n.payload)          # the adjoint recurrence, run backwards
+            acc(b, lam)
+            ga, gi = _scan_grads(n, lam)
+            if ga is not None:
+                acc(a, reduce_to(ga, d, a))
+            if gi is not None:
+                acc(n.args[2], gi)
+        elif n.op in _STAGES:
+            raise NotImplementedError("second derivatives of the matrix and scan stages")
         else:
             raise AssertionError(n.op)
     return [adj.get(w.id, Expr.const(0.0)) for w in wrt]
@@ -895,6 +992,27 @@ def _np_matop(op: str, args: list[np.ndarray], k: int, m: int) -> np.ndarray:
         G = np.transpose(_np_solve_lower_t(L, np.transpose(Y, (0, 2, 1))), (0, 2, 1))
         out = np.tril(G) + np.tril(np.transpose(G, (0, 2, 1)), -1)
     return out.reshape(N, -1)
+
+
+def _np_scan(op: str, args: list[np.ndarray], R: int, T: int, N: int) -> np.ndarray:
+    """the recurrence (``scan``) or its adjoint (``rscan``) by a plain loop over time: the checker, not a bitwise reference"""
+    def rows(v):
+        return np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, R * T)).reshape(N, R, T)
+
+    a, b = rows(args[0]), rows(args[1])
+    out = np.empty((N, R, T))
+    if op == "scan":
+        prev = np.broadcast_to(args[2][:, None] if args[2].ndim == 1 else args[2], (N, R))
+        for t in range(T):
+            prev = a[:, :, t] * prev + b[:, :, t]
+            out[:, :, t] = prev
+    else:
+        lam = b[:, :, T - 1]
+        out[:, :, T - 1] = lam
+        for t in range(T - 2, -1, -1):
+            lam = a[:, :, t + 1] * lam + b[:, :, t]
+            out[:, :, t] = lam
+    return out.reshape(N, R * T)
 
 
 def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.ndarray]:
@@ -988,6 +1106,8 @@ def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.
             elif n.op in _MATOPS:
                 args = [np.broadcast_to(val[x_.id][:, None] if val[x_.id].ndim == 1 else val[x_.id], (N, dim_len(x_.dim))) for x_ in n.args]
                 v = _np_matop(n.op, args, *n.payload)
+            elif n.op in _SCANOPS:
+                v = _np_scan(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
             else:
                 raise AssertionError(n.op)
         val[n.id] = np.asarray(v, dtype=np.float64)
@@ -1034,7 +1154,7 @@ class _Gen:
         self.level: dict[int, int] = {}
         for n in self.order:
             lv = max([self.level[a.id] for a in n.args], default=0)
-            if n.op in ("sum", "max", "gather", "segsum") + _MATOPS or (n.op in ("elem", "pad", "trunc") and n.args[0].op not in ("vparam", "data")):
+            if n.op in ("sum", "max", "gather", "segsum") + _STAGES or (n.op in ("elem", "pad", "trunc") and n.args[0].op not in ("vparam", "data")):
                 lv += 1
             self.level[n.id] = lv
         # what lives in per-chain LDS: sources of gathers (unless they are parameters or data, read in place), arguments of
@@ -1049,15 +1169,16 @@ class _Gen:
                 self.stored[n.args[0].id] = ("plain", n.args[0].dim)     # a scalar read of one element of a computed vector
             elif n.op == "stack":
                 self.stored[n.id] = ("scalars", n.dim)                   # written by the scalar code, element by element
-        # matrix stages: their operands are stored by the loops that produce them, their results by the device routine
+        # matrix and scan stages: their operands are stored by the loops that produce them (scalar operands are passed by value),
+        # their results by the device routine
         for n in self.order:
-            if n.op in _MATOPS:
+            if n.op in _STAGES:
                 for a in n.args:
-                    if self.stored.get(a.id, ("plain",))[0] == "plain":
+                    if a.dim is not None and self.stored.get(a.id, ("plain",))[0] == "plain":
                         self.stored[a.id] = ("plain", a.dim)
         for n in self.order:
-            if n.op in _MATOPS:
-                self.stored[n.id] = ("matop", n.dim)
+            if n.op in _STAGES:
+                self.stored[n.id] = ("stage", n.dim)
         # ... and segment sums that more than one loop needs.  Element-wise values are recomputed in every loop that needs them
         # (a few operations on values that are read anyway); a segment sum is an inner loop over its range.
         evaluated: dict[int, set[int]] = {}     # segment sum -> the levels of the loops that evaluate it
@@ -1070,7 +1191,7 @@ class _Gen:
                 if n.dim is None or n.id in seen:
                     continue
                 seen.add(n.id)
-                if n.op == "stack" or n.op in _MATOPS or (n.id in self.stored and self.level[n.id] < lv[1]):
+                if n.op == "stack" or n.op in _STAGES or (n.id in self.stored and self.level[n.id] < lv[1]):
                     continue               # read from LDS
                 if n.op == "segsum":
                     evaluated.setdefault(n.id, set()).add(lv[1])
@@ -1096,7 +1217,7 @@ class _Gen:
                 seen.add(n.id)
                 if n.op == "vparam":
                     reads.setdefault(n.id, set()).add(key)
-                if n.op in ("stack", "gather", "segsum", "pad", "trunc") + _MATOPS or (n.id in self.stored and self.level[n.id] < key[1]):
+                if n.op in ("stack", "gather", "segsum", "pad", "trunc") + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
                     continue
                 stack.extend(n.args)
         for nid, loops in reads.items():
@@ -1113,7 +1234,7 @@ class _Gen:
                 a = n.args[0]
                 roots.setdefault((id(a.dim), self.level[a.id]), []).append(a)
         for key, (how, _) in self.stored.items():
-            if how in ("scalars", "matop"):
+            if how in ("scalars", "stage"):
                 continue
             node = by_id[key[1] if isinstance(key, tuple) else key]
             roots.setdefault((id(node.dim), self.level[node.id]), []).append(node)
@@ -1137,6 +1258,8 @@ class _Gen:
             emit(_DIGAMMA_SOURCE)
         if any(n.op in _MATOPS for n in self.order):
             emit('#include "chain_linalg.h"')
+        if any(n.op in _SCANOPS for n in self.order):
+            emit('#include "chain_scan.h"')
         emit(f"__device__ double {self.fn_name}(const NphipData& data, int dim, const double* x, double* g, double* lds, const double* shared, int lane) {{")
         # dimension lengths, data pointers (shared LDS where staged, else global), LDS scratch
         for d in m._dims.values():
@@ -1211,15 +1334,15 @@ class _Gen:
                 emit("    }")
                 emit("    nphip_chain_barrier();")
             for n in self.order:
-                if n.op in _MATOPS and self.level[n.id] == lv:
-                    emit(self.matop_call(n))
+                if n.op in _STAGES and self.level[n.id] == lv:
+                    emit(self.matop_call(n) if n.op in _MATOPS else self.scan_call(n))
             mark(f"scalars of level {lv}")
             # loops of this level, one per dimension that has something to produce here
             for d in m._dims.values():
                 sums = [n for n in self.order if n.op in ("sum", "max") and n.args[0].dim is d and self.level[n.args[0].id] == lv]
                 stores = []
                 for key, (how, sd) in self.stored.items():
-                    if sd is not d or how in ("scalars", "matop"):
+                    if sd is not d or how in ("scalars", "stage"):
                         continue
                     node_id = key[1] if isinstance(key, tuple) else key
                     if self.level[node_id] == lv:
@@ -1257,6 +1380,22 @@ class _Gen:
         fn = {"chol": f"cholesky<{k}>", "trsv": f"solve_lower<{k}, {m}>", "trsv_t": f"solve_lower_t<{k}, {m}, {m}, 1>",
               "trsv_gl": f"solve_lower_adj_l<{k}, {m}>", "chol_adj": f"cholesky_adj<{k}>"}[n.op]
         return f"    nphip_la::{fn}({args}, {out}, lane);"
+
+    # ---- scan stages (csrc/chain_scan.h; the routine ends with the chain's barrier)
+    def scan_call(self, n: Expr) -> str:
+        R, T = n.payload
+        a, v = n.args[0], n.args[1]
+        init = n.args[2] if n.op == "scan" else Expr.const(0.0)
+        kind = "A_ONE" if a.is_const(1.0) else ("A_SCALAR" if a.dim is None else "A_ARRAY")
+        none = "(const double*)nullptr"
+        coef = self.store_name[a.id] if a.dim is not None else none
+        a_s = self.sref(a) if a.dim is None else "1.0"
+        irow = init.dim is not None
+        i_arr = self.store_name[init.id] if irow else none
+        i_s = "0.0" if irow else self.sref(init)
+        rev = "true" if n.op == "rscan" else "false"
+        return (f"    nphip_scan::linear_recurrence<{R}, {T}, nphip_scan::{kind}, {rev}, {'true' if irow else 'false'}>"
+                f"({coef}, {a_s}, {self.store_name[v.id]}, {i_arr}, {i_s}, {self.store_name[n.id]}, lane);")
 
     # ---- scalars
     def sref(self, n: Expr) -> str:
@@ -1326,7 +1465,7 @@ class _Gen:
                 elif n.op == "datacol":
                     mname, c, K = n.payload
                     stages[0].append(f"        const double {name} = D_{mname}[j_{u} * {K} + {c}];")
-                elif n.op == "stack" or n.op in _MATOPS:
+                elif n.op == "stack" or n.op in _STAGES:
                     stages[0].append(f"        const double {name} = {self.store_name[n.id]}[j_{u}];")
                 elif n.op == "gather":
                     src, index = n.args[0], n.payload
@@ -1533,6 +1672,7 @@ class Model:
             if size is None:
                 raise ValueError(f"dimension {name!r} is not known yet: give its size")
             d = self._dims[name] = Dim(name, int(size))
+            d._model = weakref.ref(self)
         elif size is not None and d.size is not None and d.size != int(size):
             raise ValueError(f"dimension {name!r} has size {d.size}, not {size}")
         return d
@@ -1541,6 +1681,7 @@ class Model:
         d = self._dims.get(name)
         if d is None:
             d = self._dims[name] = Dim(name, None, runtime_len=array_name, runtime_div=div)   # its length is that of its first data array
+            d._model = weakref.ref(self)
         elif d.size is not None and d.size != n:
             raise ValueError(f"data on dimension {name!r} must have length {d.size}")
         elif d.size is None and d.len_py(self._data) != n:
@@ -1587,7 +1728,7 @@ class Model:
         r, c = self.dim(rows), self.dim(cols)
         if r.size is None or c.size is None:
             raise ValueError("a product needs two dimensions of fixed size")
-        self.dim(name, r.size * c.size)
+        self.dim(name, r.size * c.size).factors = (r, c)
         e = np.arange(r.size * c.size)
         to_r = self.index(f"{name}_row", e // c.size, dim=name, into=rows)
         to_c = self.index(f"{name}_col", e % c.size, dim=name, into=cols)
@@ -1781,6 +1922,9 @@ class Model:
     def index(self, name: str, values, dim: str, into: str) -> Index:
         """Integer data: ``values[i]`` is the element of dimension ``into`` that element ``i`` of ``dim`` belongs to."""
         self._check_new_data(name)
+        return self._add_index(name, values, dim, into)
+
+    def _add_index(self, name: str, values, dim: str, into: str) -> Index:
         a = np.ascontiguousarray(values, dtype=np.int32)
         into_d = self.dim(into)
         if into_d.size is None:
@@ -1794,6 +1938,30 @@ class Model:
         self._data_fields.append((name + "__rows", "int", into_d))
         self._derive(name)
         return ix
+
+    def _scan_aux(self, d: Dim, R: int, T: int, rows: Dim | None) -> list:
+        """what the gradient of a scan over R rows of T elements on ``d`` reads: [index of element t - 1 (t = 0: itself), data that is 1
+        on the first element of every row (R > 1), index of the row (``rows``: an init per row)] — registered once per (d, T); the
+        names hold a double underscore, which no user data can"""
+        aux = d._scan_aux.get(T)
+        e = np.arange(R * T)
+        if aux is None:
+            name = f"{d.name}__prev{T}"
+            self._data[name] = np.where(e % T == 0, e, e - 1).astype(np.int32)
+            self._data_fields.append((name, "int", d))
+            first = None
+            if R > 1:
+                fname = f"{d.name}__first{T}"
+                self._data[fname] = (e % T == 0).astype(np.float64)
+                self._data_fields.append((fname, "double", d))
+                first = Expr("data", (), d, fname)
+            aux = d._scan_aux[T] = [Index(name, d, d), first, None]
+        if rows is not None and aux[2] is None:
+            if d.factors is not None and d.factors[0] is rows:
+                aux[2] = self._products[d.name][2]
+            else:
+                aux[2] = self._add_index(f"{d.name}__row{T}", e // T, d.name, rows.name)
+        return aux
 
     def _check_new_data(self, name):
         if not name.isidentifier() or "__" in name:
@@ -2185,6 +2353,13 @@ class Model:
         else:
             out_names, out_shapes = names, shapes
         egen = _Gen(self, Expr.const(0.0), [], waves_per_chain, outputs=offs, fn_name="nphip_expand") if (fixed and det) else None
+        if egen is not None and any(n.op in _SCANOPS for n in egen.order):
+            # (the generated expand keeps its arrays in LDS, (4 rows per workgroup with one wave per row) + the staged data: a long scan
+            #  that does not fit is expanded on the host)
+            rows_per_block = 4 if waves_per_chain == 1 else 1
+            per_row = sum(d.len_py(self._data) for _, (_, d) in egen.stored.items())
+            if 8 * (rows_per_block * per_row + self._shared_doubles(self._data)) > self.LDS_BYTES - 2048:
+                egen = None
         expand_src = ""
         if egen is not None:
             egen.spilled = []
