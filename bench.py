@@ -10,6 +10,10 @@ positions stored (``--phase tuning`` times inside warm-up instead, as round 1 di
 steps, then EXACTLY K timed steps bracketed by barrier + synchronize on both sides; time = max over
 ranks; rank 0 prints ONE JSON line.  With no ``--steps`` K is sized for a timed region of ~1.2 s.
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, ``--dump-outputs`` if given, and the line
+(with `roofline`, `tuning_phase` and `ranks`, which take no run of their own).  ``--full`` adds every other leg below
+(`config5_shard`, `job`, `other_configs`, the CPU baselines) after the headline, as before; ``--no-*`` leave single legs out of it.
+
 Workload (``config.workload``): BASELINE.json configs[1] — 1000-dimensional correlated Gaussian
 (AR(1) rho = 0.9 with per-dimension scales exp(N(0,1)) from numpy.random.default_rng(20260926),
 analytic logp/grad fused in-kernel), 1024 chains per GPU, adaptation "diag", target_accept 0.8,
@@ -17,7 +21,7 @@ maxdepth 10, U(-2,2) initial points.  Inputs are generated on the host once and 
 before the timed region.  Multi-GPU is weak scaling: 1024 chains per GPU, chain ids offset per rank,
 no collective in the data path (only the timing all-reduce).
 
-Extra objects in the JSON line:
+Extra objects in the JSON line (`cpu_baseline*`, `job`, `config5_shard` and `other_configs` with ``--full`` only):
   roofline      — what bounds the dominant kernel and how close it runs to that bound, with `frac` <= 1:
                   * register-resident kernels (D <= 4096: the chain state stays in VGPRs / LDS, so the kernel moves LESS than the
                     SURVEY.md §8d "algorithmic" 40 * D bytes per leapfrog and HBM is not its limit): `bound` = "issue" — one wave
@@ -96,11 +100,13 @@ def parse(argv=None):
     p.add_argument("--seed", type=int, default=20260926)
     p.add_argument("--phase", choices=("sampling", "tuning"), default="sampling",
                    help="where the timed region lies: after warm-up (default; positions are stored) or inside it")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-job", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run the other legs: config-5 shard, whole job with ESS, configs 3 / 4 / 2 (ii), CPU baselines")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    p.add_argument("--no-job", action="store_true", help="--full without the whole tune 400 + draws 1000 job")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
-    p.add_argument("--no-other-configs", action="store_true", help="skip the bounded runs of configs 3, 4, 2 (ii) (N = 1)")
-    p.add_argument("--no-config5", action="store_true", help="skip the config-5 shard leg (10 000 dimensions, roofline + trace gather)")
+    p.add_argument("--no-other-configs", action="store_true", help="--full without the bounded runs of configs 3, 4, 2 (ii) (N = 1)")
+    p.add_argument("--no-config5", action="store_true", help="--full without the config-5 shard leg (10 000 dimensions, roofline + trace gather)")
     p.add_argument("--config5-dim", type=int, default=10000)
     p.add_argument("--config5-launches", type=int, default=10)
     p.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -1063,7 +1069,8 @@ def main(argv=None):
         out["stub"] = "engine replaced by a test stand-in: this line exercises bench.py's multi-rank plumbing and measures nothing"
     if tuning_phase is not None:
         out["tuning_phase"] = tuning_phase
-    if not args.no_config5 and args.dim != args.config5_dim:
+    # Everything below measures something other than the headline and takes runs of its own (a minute or two): only with --full
+    if args.full and not args.no_config5 and args.dim != args.config5_dim:
         try:
             out["config5_shard"] = config5_shard(env, args)   # (collective: every rank takes part)
         except InvalidRegion as e:    # (raised on every rank together: see timed_launches)
@@ -1072,12 +1079,13 @@ def main(argv=None):
             if world > 1:
                 raise   # a rank that drops out of a collective must not leave the others waiting
             out["config5_shard"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_job and args.dim <= 2048 and not env.stub:
+    full_n1 = args.full and rank == 0 and world == 1 and not env.stub
+    if full_n1 and not args.no_job and args.dim <= 2048:
         dims = sorted(set(np.linspace(0, args.dim - 1, 12).astype(int).tolist() + [int(np.argmax(model.diag)), int(np.argmin(model.diag))]))
         out["job"] = run_job(hip, model, args, device, 0, dims, world)
-    if rank == 0 and world == 1 and not args.no_other_configs and not env.stub:
+    if full_n1 and not args.no_other_configs:
         out["other_configs"] = other_configs(env, args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not env.stub:
+    if full_n1 and not args.no_cpu_baseline:
         tuned, port = cpu_baseline(model, args.seed, args.cpu_seconds)
         out["cpu_baseline"] = port
         out["gpu_over_cpu"] = out["value"] / port["value"]

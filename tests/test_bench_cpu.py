@@ -97,11 +97,11 @@ STUB = os.path.join(ROOT, "tests", "bench_stub_engine.py")
 
 
 def test_gpus_n_spawns_its_own_ranks_and_gathers_in_global_chain_order():
-    """`python bench.py --gpus 2` with no RANK in the environment starts two ranks itself (torch.distributed.run,
+    """`python bench.py --gpus 2 --full` with no RANK in the environment starts two ranks itself (torch.distributed.run,
     127.0.0.1), shards the chains by global id, runs the config-5 shard leg with ONE gather to rank 0, and rank 0 prints one line.
     The engine is a stand-in (tests/bench_stub_engine.py, gloo): this pins the plumbing, it measures nothing."""
     r, out, lines = _run_bench("--gpus", "2", "--engine-stub", STUB, "--chains", "8", "--dim", "16", "--config5-dim", "32",
-                               "--steps", "3", "--warmup", "1", "--config5-launches", "2")
+                               "--steps", "3", "--warmup", "1", "--config5-launches", "2", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1                                        # ONE JSON line, from rank 0
     assert out["n_gpus"] == 2 and out["data"] == "stub" and "stub" in out
@@ -122,12 +122,28 @@ def test_gpus_n_spawns_its_own_ranks_and_gathers_in_global_chain_order():
 def test_stub_gather_is_in_global_chain_order():
     """The same leg in one process (no torch.distributed.run): a one-rank group is created for the gather."""
     r, out, _ = _run_bench("--engine-stub", STUB, "--chains", "4", "--dim", "16", "--config5-dim", "32", "--steps", "2", "--warmup", "1",
-                           "--config5-launches", "1")
+                           "--config5-launches", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     assert out["n_gpus"] == 1 and out["ranks"]["launched_by"] == "single process"
     c5 = out["config5_shard"]
     assert c5["gather"]["collective_ranks"] == 1 and c5["gather"]["check"]["chains_gathered"] == 4
     assert c5["gather"]["arrays"]["draws"][0] == 4 and c5["gather"]["arrays"]["draw_mean"] == [4, 32]
+
+
+def test_a_plain_run_is_the_headline_alone():
+    """Without --full, bench.py sets up, warms up, times its steps and prints the line: no leg after the headline (the config-5 shard
+    and the process group its gather creates, the N = 1 legs), with the headline fields unchanged."""
+    r, out, lines = _run_bench("--engine-stub", STUB, "--chains", "4", "--dim", "16", "--config5-dim", "32", "--steps", "2", "--warmup", "1",
+                               "--config5-launches", "1")
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(lines) == 1 and r.stdout.count("\n") == 1
+    assert not {"config5_shard", "job", "other_configs", "cpu_baseline", "cpu_baseline_tuned"} & set(out)
+    assert out["ranks"]["backend"] is None and out["ranks"]["collective_ranks"] == 1
+    assert out["metric"] == "leapfrog steps/sec (all chains)" and out["unit"] == "leapfrog steps/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f64" and out["steps"] == 2 and out["warmup"] == 1
+    # 4 chains x 2 timed launches of the stub's 8 leapfrogs over the timed region
+    assert abs(out["value"] - 4 * 2 * 8 / (out["ms_per_step"] * 2 / 1000)) < 1e-6 * out["value"]
+    assert "tuning_phase" in out and "roofline" in out
 
 
 def test_dump_outputs_writes_every_chains_latest_draw(tmp_path):
@@ -169,11 +185,11 @@ def test_world_size_must_agree_with_gpus():
 
 
 def test_eight_ranks_through_the_spawn_path_with_config5s_layout_scaled_down():
-    """`bench.py --gpus 8` through its own spawn path (eight gloo ranks, stand-in engine): config 5's layout — every rank owns
+    """`bench.py --gpus 8 --full` through its own spawn path (eight gloo ranks, stand-in engine): config 5's layout — every rank owns
     a contiguous block of chains of a long row — scaled down; ONE gather per array into ONE buffer on the root (root memory = 1 x payload),
     chains in global order, the line says collective_ranks 8, and only rank 0 prints."""
     r, out, lines = _run_bench("--gpus", "8", "--engine-stub", STUB, "--chains", "6", "--dim", "16", "--config5-dim", "200",
-                               "--steps", "2", "--warmup", "1", "--config5-launches", "2", timeout=480)
+                               "--steps", "2", "--warmup", "1", "--config5-launches", "2", "--full", timeout=480)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1 and out["n_gpus"] == 8
     ranks = out["ranks"]
