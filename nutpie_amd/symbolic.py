@@ -33,8 +33,10 @@ recurrence, ``init`` a scalar or a value on ``rows``), ``cumsum(x, along=None)``
 path, a GARCH(1, 1) variance or an exponential-smoothing level — a stage between loops that one device routine runs on the chain's
 wave(s) (``csrc/chain_scan.h``), up to four waves per chain.
 
-Also: ``m.matrix("X", values, dim="obs", cols="coef")`` and ``X @ beta`` (a design matrix: lowered to a sum over its columns, the
-transposed product to one wave-wide sum per column); ``lower=`` / ``upper=`` / both (log and logit-interval transforms with their
+Also: ``m.matrix("X", values, dim="obs", cols="coef")`` and ``X @ beta`` (a design matrix: with up to 63 columns lowered to a sum over
+its columns, the transposed product to one wave-wide sum per column; with more — or ``stage=True``, or a ``B`` with several right-hand
+sides on a ``product(coef, rhs)`` — a stage between loops that reads the matrix from L2, ``csrc/chain_matvec.h``, DESIGN.md §11.7,
+with ``X.T @ g`` its transpose and ``column`` / ``pack_columns`` the columns of an n x R value); ``lower=`` / ``upper=`` / both (log and logit-interval transforms with their
 Jacobians); densities ``normal``, ``halfnormal``, ``student_t``, ``cauchy``, ``halfcauchy``, ``exponential``, ``lognormal``, ``gamma``,
 ``bernoulli_logit``, ``poisson_log``; ``compile(waves_per_chain=...)`` (default: from the LDS the model needs); ``Model.profile()``
 (cycle attribution of the generated code on the GPU).
@@ -69,7 +71,7 @@ __all__ = ["Model", "Expr", "Matrix", "exp", "log", "log1p", "sqrt", "softplus",
            "inverse_gamma_lpdf", "beta_lpdf", "laplace_lpdf", "logistic_lpdf", "weibull_lpdf", "uniform_lpdf",
            "bernoulli_logit_lpmf", "binomial_logit_lpmf", "negative_binomial_log_lpmf", "poisson_log_lpmf", "dirichlet_lpdf", "flat_lpdf",
            "cholesky", "solve_lower", "log_det_chol", "mvnormal_lpdf", "lkj_corr_cholesky_lpdf",
-           "linear_recurrence", "cumsum"]
+           "linear_recurrence", "cumsum", "column", "pack_columns"]
 
 _WAVE = 64
 _SEG_BATCH = os.environ.get("NUTPIE_AMD_SEG_MODE", "select") != "loop"   # (developer switch: "loop" = plain loops over a segment)
@@ -80,11 +82,12 @@ _UNROLL = 4   # iterations of a loop whose reads are issued together (a lone wav
 class Dim:
     """A named coordinate of the model: the range one wave-wide loop runs over."""
 
-    def __init__(self, name: str, size, runtime_len: str | None = None, runtime_div: int = 1):
+    def __init__(self, name: str, size, runtime_len: str | None = None, runtime_div: int = 1, runtime_mul: int = 1):
         self.name = name
         self.size = size                  # int, or None for a data dimension whose length comes from the data block
         self.runtime_len = runtime_len    # the data array whose length is the dimension's (times runtime_div: a matrix's rows)
         self.runtime_div = runtime_div
+        self.runtime_mul = runtime_mul    # (the product of a data dimension with a fixed-size one: that many values per element)
         self.factors: tuple[Dim, Dim] | None = None   # (rows, cols) of a Model.product
         self._model = None                # (weak) the Model that declared it: where a scan's gradient registers its shifted read
         self._scan_aux: dict[int, tuple] = {}   # row length T -> (index of element t - 1, "first element of a row" data or None)
@@ -92,10 +95,10 @@ class Dim:
     def len_c(self) -> str:
         if self.size is not None:
             return str(self.size)
-        return f"data.n_{self.runtime_len}" + (f" / {self.runtime_div}" if self.runtime_div != 1 else "")
+        return f"data.n_{self.runtime_len}" + (f" / {self.runtime_div}" if self.runtime_div != 1 else "") + (f" * {self.runtime_mul}" if self.runtime_mul != 1 else "")
 
     def len_py(self, data) -> int:
-        return self.size if self.size is not None else int(np.asarray(data[self.runtime_len]).size) // self.runtime_div
+        return self.size if self.size is not None else int(np.asarray(data[self.runtime_len]).size) // self.runtime_div * self.runtime_mul
 
     def __repr__(self):
         return f"Dim({self.name})"
@@ -110,23 +113,88 @@ class Index:
 
 class Matrix:
     """Float data with one row per element of ``dim`` and one column per element of ``cols`` (a design matrix).  ``X @ v`` with ``v``
-    on ``cols`` is the linear predictor on ``dim``: a sum over the columns of (column x element of v), so that its transpose —
-    the gradient with respect to ``v`` — is one wave-wide sum per column."""
+    on ``cols`` is the linear predictor on ``dim``.  With up to ``STAGE_ABOVE`` columns it is a sum over the columns of (column
+    x element of v), so that its transpose — the gradient with respect to ``v`` — is one wave-wide sum per column; with more (or
+    ``Model.matrix(..., stage=True)``) it is a stage between loops that one device routine runs (``csrc/chain_matvec.h``, DESIGN.md
+    §11.7), and ``X.T @ g`` with ``g`` on ``dim`` the transposed product."""
 
-    def __init__(self, name: str, dim: Dim, cols: Dim):
-        self.name, self.dim, self.cols = name, dim, cols
+    #: the automatic lowering keeps the sum over the columns up to this many columns: the stage from 64 on, the smallest measured
+    #: width where it samples faster (logistic regression, n = 2000, 512 chains: 1.46 against 0.91 M leapfrogs/s; at 32 columns 1.64
+    #: against 5.46 — profiles/matvec_wide_regression.txt)
+    STAGE_ABOVE = 63
+
+    def __init__(self, name: str, dim: Dim, cols: Dim, stage: bool | None = None, model=None):
+        self.name, self.dim, self.cols, self.stage = name, dim, cols, stage
+        self._model = model               # (weak) the Model that holds the data: a stage registers the transposed copy there
 
     def column(self, c: int) -> "Expr":
         return Expr("datacol", (), self.dim, (self.name, int(c), self.cols.size))
 
+    @property
+    def T(self) -> "_MatrixT":
+        """The transposed matrix: ``X.T @ g`` with ``g`` on the rows' dimension is a value on ``cols``."""
+        return _MatrixT(self)
+
+    def _staged_product(self) -> bool:
+        return self.stage if self.stage is not None else self.cols.size > Matrix.STAGE_ABOVE
+
+    def _register_stage(self):
+        m = self._model() if self._model is not None else None
+        if m is None:
+            raise ValueError(f"matrix {self.name!r} belongs to no Model")
+        m._matrix_stage(self)
+
+    def _rhs(self, v, outer: Dim, what: str) -> Dim | None:
+        """the dimension of the right-hand sides when ``v`` lives on a ``Model.product(outer, rhs)``, None when it lives on ``outer``"""
+        if isinstance(v, Expr) and v.dim is outer:
+            return None
+        if not isinstance(v, Expr) or v.dim is None or v.dim.factors is None or v.dim.factors[0] is not outer:
+            raise ValueError(f"matrix {self.name!r}{what} multiplies a vector on dimension {outer.name!r} (or a value on a product({outer.name!r}, right-hand sides))")
+        rhs = v.dim.factors[1]
+        if rhs.size > MAX_RHS:
+            raise ValueError(f"matrix {self.name!r}{what} multiplies up to {MAX_RHS} right-hand sides at once ({rhs.name!r} has {rhs.size})")
+        return rhs
+
+    def _product_dim(self, outer: Dim, rhs: Dim) -> Dim:
+        return self._model().product(outer.name, rhs.name)
+
+    def times(self, B: "Expr", out: Dim, R: int) -> "Expr":
+        """``X B`` for ``B`` on ANY fixed-size dimension of K x R elements (row-major), the n x R result on ``out`` (n x R elements) —
+        what a front end that keeps its tensors flat calls (the torch tracer); ``X @ B`` is this on a ``Model.product``."""
+        K = self.cols.size
+        if not isinstance(B, Expr) or B.dim is None or B.dim.size != K * R or not 1 <= R <= MAX_RHS or out.len_py(self._model()._data) != self.dim.len_py(self._model()._data) * R:
+            raise ValueError(f"matrix {self.name!r} times a K x R value: K = {K}, up to {MAX_RHS} right-hand sides, the result n x R")
+        self._register_stage()
+        return Expr("matvec", (B,), out, (self.name, K, int(R)))
+
     def __matmul__(self, v) -> "Expr":
-        if not isinstance(v, Expr) or v.dim is not self.cols:
-            raise ValueError(f"matrix {self.name!r} multiplies a vector on dimension {self.cols.name!r}")
+        rhs = self._rhs(v, self.cols, "")
+        if rhs is not None:       # K x R coefficients: always the stage, the result n x R on product(rows, right-hand sides)
+            self._register_stage()
+            return Expr("matvec", (v,), self._product_dim(self.dim, rhs), (self.name, self.cols.size, rhs.size))
+        if self._staged_product():
+            self._register_stage()
+            return Expr("matvec", (v,), self.dim, (self.name, self.cols.size, 1))
         total = None
         for c in range(self.cols.size):
             term = self.column(c) * elem(v, c)
             total = term if total is None else total + term
         return total
+
+
+class _MatrixT:
+    """``X.T``: what ``X.T @ g`` multiplies with (always the stage: the transposed product has no other form)."""
+
+    def __init__(self, matrix: Matrix):
+        self.matrix = matrix
+
+    def __matmul__(self, g) -> "Expr":
+        X = self.matrix
+        rhs = X._rhs(g, X.dim, " transposed")
+        X._register_stage()
+        if rhs is not None:
+            return Expr("matvec_t", (g,), X._product_dim(X.cols, rhs), (X.name, X.cols.size, rhs.size))
+        return Expr("matvec_t", (g,), X.cols, (X.name, X.cols.size, 1))
 
 
 class Expr:
@@ -229,6 +297,8 @@ def _binary(op: str, a: Expr, b: Expr) -> Expr:
             return b
         if b.is_const(0.0):
             return a
+        if a.op == "rowpack" and b.op == "rowpack" and a.dim is b.dim:     # (the adjoints of the columns of one value, collected)
+            return Expr("rowpack", tuple(_binary("add", x, y) for x, y in zip(a.args, b.args)), a.dim, None)
         if a is b:
             return _binary("mul", Expr.const(2.0), a)
     elif op == "sub":
@@ -533,7 +603,37 @@ def lkj_corr_cholesky_lpdf(L, eta: float) -> Expr:
 # gradient emits: lambda_t = a_{t+1} lambda_{t+1} + xbar_t, lambda_{T-1} = xbar_{T-1}.  ``a`` is a value on the dimension, a scalar, or
 # the constant 1 (a prefix sum); ``init`` a scalar or a value on the rows.  payload = (R, T).
 _SCANOPS = ("scan", "rscan")
-_STAGES = _MATOPS + _SCANOPS
+# Data-matrix stages: ``matvec`` E = X B (arg B on the matrix's columns, result on its rows) and ``matvec_t`` C = X^T G, each the
+# other's adjoint (csrc/chain_matvec.h).  payload = (name of the matrix, K columns, R right-hand sides).
+_MVOPS = ("matvec", "matvec_t")
+MAX_RHS = 16        # the right-hand sides of one product: that many accumulators per row block of a lane
+
+
+# A value on ``product(rows, rhs)`` (row-major, R = rhs.size values per row) and the R values on ``rows`` that are its columns:
+# ``column(E, r)`` reads column r (like a gather: from the stored array, in a loop over the rows), ``pack_columns([g_0 .. g_{R-1}],
+# dim)`` is the value whose columns the g_r are (stored by the loop over the rows that computes them) — each the other's adjoint.
+# What is element-wise ALONG the right-hand sides (a softmax over the classes) is written with these two, on the rows' loop.
+def column(E, r: int) -> Expr:
+    """Column ``r`` of a value on a ``Model.product(rows, rhs)``: a value on ``rows``."""
+    E = Expr.wrap(E)
+    if E.dim is None or E.dim.factors is None or not 0 <= int(r) < E.dim.factors[1].size:
+        raise ValueError("column(): a value on a Model.product(rows, rhs) and a column inside it")
+    if E.op == "rowpack":
+        return E.args[int(r)]
+    return Expr("rhscol", (E,), E.dim.factors[0], int(r))
+
+
+def pack_columns(columns, dim: Dim) -> Expr:
+    """The value on ``dim`` = ``Model.product(rows, rhs)`` whose columns are the given values on ``rows`` (or scalars)."""
+    columns = [Expr.wrap(c) for c in columns]
+    if dim.factors is None or len(columns) != dim.factors[1].size or any(c.dim is not None and c.dim is not dim.factors[0] for c in columns):
+        raise ValueError("pack_columns(): one value on the rows (or scalar) per column of a Model.product(rows, rhs)")
+    if all(c.is_const(0.0) for c in columns):
+        return Expr.const(0.0)
+    return Expr("rowpack", tuple(columns), dim, None)
+
+
+_STAGES = _MATOPS + _SCANOPS + _MVOPS
 
 
 def _scan(a, b, init, R: int, T: int, rows: Dim | None = None) -> Expr:
@@ -839,6 +939,11 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
             for c, a_ in enumerate(n.args):
                 acc(a_, elem(g, c))
             continue
+        if n.op == "rowpack":
+            rows = n.dim.factors[0]
+            for c, a_ in enumerate(n.args):
+                acc(a_, reduce_to(g if g.dim is None else column(g, c), rows, a_))
+            continue
         d = n.dim
         a = n.args[0]
         b = n.args[1] if len(n.args) > 1 else None
@@ -921,6 +1026,13 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
                 acc(a, reduce_to(ga, d, a))
             if gi is not None:
                 acc(n.args[2], gi)
+        elif n.op == "rhscol":
+            zero = Expr.const(0.0)
+            acc(a, pack_columns([_bcast(g, d) if c == n.payload else zero for c in range(a.dim.factors[1].size)], a.dim))
+        elif n.op == "matvec":
+            acc(a, Expr("matvec_t", (_bcast(g, d),), a.dim, n.payload))   # B-bar = X^T E-bar
+        elif n.op == "matvec_t":
+            acc(a, Expr("matvec", (_bcast(g, d),), a.dim, n.payload))     # G-bar = X C-bar
         elif n.op in _STAGES:
             raise NotImplementedError("second derivatives of the matrix and scan stages")
         else:
@@ -1108,6 +1220,20 @@ def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.
                 v = _np_matop(n.op, args, *n.payload)
             elif n.op in _SCANOPS:
                 v = _np_scan(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
+            elif n.op == "rhscol":
+                R = n.args[0].dim.factors[1].size
+                v = np.broadcast_to(a[:, None] if a.ndim == 1 else a, (N, dim_len(n.args[0].dim))).reshape(N, -1, R)[:, :, n.payload]
+            elif n.op == "rowpack":
+                rows = dim_len(n.dim.factors[0])
+                v = np.stack([np.broadcast_to(val[x_.id][:, None] if val[x_.id].ndim == 1 else val[x_.id], (N, rows)) for x_ in n.args], axis=2).reshape(N, -1)
+            elif n.op in _MVOPS:
+                name, K, R = n.payload
+                X = np.asarray(data[name], dtype=np.float64).reshape(-1, K)
+                arg = np.broadcast_to(a[:, None] if a.ndim == 1 else a, (N, dim_len(n.args[0].dim)))
+                if n.op == "matvec":      # [N, K, R] -> [N, n, R]
+                    v = np.einsum("ik,nkr->nir", X, arg.reshape(N, K, R)).reshape(N, -1)
+                else:                     # [N, n, R] -> [N, K, R]
+                    v = np.einsum("ik,nir->nkr", X, arg.reshape(N, -1, R)).reshape(N, -1)
             else:
                 raise AssertionError(n.op)
         val[n.id] = np.asarray(v, dtype=np.float64)
@@ -1154,7 +1280,7 @@ class _Gen:
         self.level: dict[int, int] = {}
         for n in self.order:
             lv = max([self.level[a.id] for a in n.args], default=0)
-            if n.op in ("sum", "max", "gather", "segsum") + _STAGES or (n.op in ("elem", "pad", "trunc") and n.args[0].op not in ("vparam", "data")):
+            if n.op in ("sum", "max", "gather", "segsum", "rhscol", "rowpack") + _STAGES or (n.op in ("elem", "pad", "trunc") and n.args[0].op not in ("vparam", "data")):
                 lv += 1
             self.level[n.id] = lv
         # what lives in per-chain LDS: sources of gathers (unless they are parameters or data, read in place), arguments of
@@ -1169,6 +1295,10 @@ class _Gen:
                 self.stored[n.args[0].id] = ("plain", n.args[0].dim)     # a scalar read of one element of a computed vector
             elif n.op == "stack":
                 self.stored[n.id] = ("scalars", n.dim)                   # written by the scalar code, element by element
+            elif n.op == "rhscol" and n.args[0].op != "rowpack":
+                self.stored[n.args[0].id] = ("plain", n.args[0].dim)     # a column of a value on product(rows, rhs), read in the rows' loop
+            elif n.op == "rowpack":
+                self.stored[n.id] = ("packed", n.dim)                    # written column by column by the rows' loop one level below
         # matrix and scan stages: their operands are stored by the loops that produce them (scalar operands are passed by value),
         # their results by the device routine
         for n in self.order:
@@ -1191,12 +1321,12 @@ class _Gen:
                 if n.dim is None or n.id in seen:
                     continue
                 seen.add(n.id)
-                if n.op == "stack" or n.op in _STAGES or (n.id in self.stored and self.level[n.id] < lv[1]):
+                if n.op in ("stack", "rowpack") or n.op in _STAGES or (n.id in self.stored and self.level[n.id] < lv[1]):
                     continue               # read from LDS
                 if n.op == "segsum":
                     evaluated.setdefault(n.id, set()).add(lv[1])
                     continue               # (its argument was stored by an earlier loop)
-                if n.op in ("gather", "pad", "trunc"):
+                if n.op in ("gather", "pad", "trunc", "rhscol"):
                     continue
                 stack.extend(n.args)
         for nid, levels in evaluated.items():
@@ -1217,7 +1347,7 @@ class _Gen:
                 seen.add(n.id)
                 if n.op == "vparam":
                     reads.setdefault(n.id, set()).add(key)
-                if n.op in ("stack", "gather", "segsum", "pad", "trunc") + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
+                if n.op in ("stack", "gather", "segsum", "pad", "trunc", "rhscol", "rowpack") + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
                     continue
                 stack.extend(n.args)
         for nid, loops in reads.items():
@@ -1237,6 +1367,9 @@ class _Gen:
             if how in ("scalars", "stage"):
                 continue
             node = by_id[key[1] if isinstance(key, tuple) else key]
+            if how == "packed":       # its columns are the roots, in the rows' loop one level below
+                roots.setdefault((id(node.dim.factors[0]), self.level[node.id] - 1), []).extend(a for a in node.args if a.dim is not None)
+                continue
             roots.setdefault((id(node.dim), self.level[node.id]), []).append(node)
         for _, g in self.out_vector:
             roots.setdefault((id(g.dim), self.level[g.id]), []).append(g)
@@ -1260,6 +1393,8 @@ class _Gen:
             emit('#include "chain_linalg.h"')
         if any(n.op in _SCANOPS for n in self.order):
             emit('#include "chain_scan.h"')
+        if any(n.op in _MVOPS for n in self.order):
+            emit('#include "chain_matvec.h"')
         emit(f"__device__ double {self.fn_name}(const NphipData& data, int dim, const double* x, double* g, double* lds, const double* shared, int lane) {{")
         # dimension lengths, data pointers (shared LDS where staged, else global), LDS scratch
         for d in m._dims.values():
@@ -1335,13 +1470,19 @@ class _Gen:
                 emit("    nphip_chain_barrier();")
             for n in self.order:
                 if n.op in _STAGES and self.level[n.id] == lv:
-                    emit(self.matop_call(n) if n.op in _MATOPS else self.scan_call(n))
+                    emit(self.matop_call(n) if n.op in _MATOPS else self.scan_call(n) if n.op in _SCANOPS else self.mv_call(n))
+                    if n.op in _MVOPS:
+                        mark(f"stage {n.op}<{n.payload[1]}, {n.payload[2]}> of {n.payload[0]}")
             mark(f"scalars of level {lv}")
             # loops of this level, one per dimension that has something to produce here
             for d in m._dims.values():
                 sums = [n for n in self.order if n.op in ("sum", "max") and n.args[0].dim is d and self.level[n.args[0].id] == lv]
                 stores = []
                 for key, (how, sd) in self.stored.items():
+                    if how == "packed":
+                        if sd.factors[0] is d and self.level[key] - 1 == lv:
+                            stores.append((key, how))
+                        continue
                     if sd is not d or how in ("scalars", "stage"):
                         continue
                     node_id = key[1] if isinstance(key, tuple) else key
@@ -1396,6 +1537,17 @@ class _Gen:
         rev = "true" if n.op == "rscan" else "false"
         return (f"    nphip_scan::linear_recurrence<{R}, {T}, nphip_scan::{kind}, {rev}, {'true' if irow else 'false'}>"
                 f"({coef}, {a_s}, {self.store_name[v.id]}, {i_arr}, {i_s}, {self.store_name[n.id]}, lane);")
+
+    # ---- data-matrix stages (csrc/chain_matvec.h; the routine ends with the chain's barrier)
+    def mv_call(self, n: Expr) -> str:
+        name, K, R = n.payload
+        arg, out = self.store_name[n.args[0].id], self.store_name[n.id]
+        rows = self.m._matrix_t[name].dim          # (the length the routines take is the matrix's rows, whatever R)
+        # the routines read the matrix from device memory — also a matrix that the loops of a sum over its columns read from the
+        # workgroup's staged copy in LDS (a narrow matrix with `X @ beta` unrolled and `X.T @ g` beside it)
+        if n.op == "matvec":
+            return f"    nphip_mv::times<{K}, {R}>(data.{name}__t, {arg}, {out}, n_{rows.name}, lane);"
+        return f"    nphip_mv::times_t<{K}, {R}>(data.{name}, {arg}, {out}, n_{rows.name}, lane);"
 
     # ---- scalars
     def sref(self, n: Expr) -> str:
@@ -1465,8 +1617,11 @@ class _Gen:
                 elif n.op == "datacol":
                     mname, c, K = n.payload
                     stages[0].append(f"        const double {name} = D_{mname}[j_{u} * {K} + {c}];")
-                elif n.op == "stack" or n.op in _STAGES:
+                elif n.op in ("stack", "rowpack") or n.op in _STAGES:
                     stages[0].append(f"        const double {name} = {self.store_name[n.id]}[j_{u}];")
+                elif n.op == "rhscol":
+                    src = n.args[0]
+                    stages[0].append(f"        const double {name} = {self.store_name[src.id]}[j_{u} * {src.dim.factors[1].size} + {n.payload}];")
                 elif n.op == "gather":
                     src, index = n.args[0], n.payload
                     iname = f"k{index.name}_{u}"
@@ -1513,6 +1668,11 @@ class _Gen:
             guard = f"if (i_{u} < n_{d.name}) "
             for key, how in stores:
                 node = by_id[key[1] if isinstance(key, tuple) else key]
+                if how == "packed":
+                    R_ = len(node.args)
+                    for c, a_ in enumerate(node.args):
+                        stages[4].append(f"        {guard}{self.store_name[key]}[i_{u} * {R_} + {c}] = {val(a_)};")
+                    continue
                 v = val(node)
                 if how == "grouped":
                     index_name = key[2]
@@ -1663,6 +1823,8 @@ class Model:
         self._transforms: dict[str, tuple] = {}      # parameter -> (kind, lower, upper, shape): what initial_point inverts
         self._initvals: dict[str, Any] = {}          # parameter -> the constrained value its chains start around (PyMC's `initval`)
         self._staged = True
+        self._matrix_t: dict[str, Matrix] = {}       # matrices that a stage multiplies with: they keep a transposed copy, <name>__t
+        self._unstaged: set[str] = set()             # data that only stages read: never staged into LDS, not counted against STAGE_LIMIT
         self._specialize = True     # lengths of data dimensions are compile-time constants of the generated source (compile(specialize=...))
 
     # ---- declarations
@@ -1688,9 +1850,11 @@ class Model:
             raise ValueError(f"data on dimension {name!r} must have length {d.len_py(self._data)}")
         return d
 
-    def matrix(self, name: str, values, dim: str, cols: str) -> Matrix:
+    def matrix(self, name: str, values, dim: str, cols: str, stage: bool | None = None) -> Matrix:
         """A float data matrix with one row per element of ``dim`` and one column per element of ``cols`` (a fixed-size dimension:
-        the coefficients'): ``X @ beta`` is the linear predictor.  ``with_data`` can replace it (same number of columns)."""
+        the coefficients'): ``X @ beta`` is the linear predictor.  ``with_data`` can replace it (same number of columns).
+        ``stage``: how ``X @ beta`` is lowered — None: a sum over the columns up to ``Matrix.STAGE_ABOVE`` columns, the device
+        routine of ``csrc/chain_matvec.h`` beyond; True / False force one of the two."""
         self._check_new_data(name)
         a = np.ascontiguousarray(values, dtype=np.float64)
         if a.ndim != 2:
@@ -1702,7 +1866,26 @@ class Model:
         self._matrix_cols[name] = int(a.shape[1])
         d = self._data_dim(dim, name, a.shape[0], div=int(a.shape[1]))
         self._data_fields.append((name, "double", d))
-        return Matrix(name, d, cd)
+        return Matrix(name, d, cd, stage, weakref.ref(self))
+
+    def _matrix_stage(self, X: Matrix) -> None:
+        """a stage multiplies with ``X``: the model keeps the transposed copy (K x n, ``<name>__t`` — a double underscore, which no user
+        data can hold) that ``with_data`` regenerates, so that both products read consecutive addresses from consecutive lanes"""
+        if X.name in self._matrix_t:
+            return
+        K = self._matrix_cols[X.name]
+        self._matrix_t[X.name] = X
+        self._data[X.name + "__t"] = np.ascontiguousarray(self._data[X.name].reshape(-1, K).T).reshape(-1)
+        self._matrix_cols[X.name + "__t"] = K
+        self._data_fields.append((X.name + "__t", "double", X.dim))
+
+    def _plan_staging(self, roots: list[Expr]) -> None:
+        """which data the workgroup stages into LDS: everything while it fits ``STAGE_LIMIT`` — except the matrices that only stages
+        read (and their transposed copies): those are read from L2 and do not count"""
+        order = _topo(roots)
+        by_column = {n.payload[0] for n in order if n.op == "datacol"}
+        self._unstaged = {name + "__t" for name in self._matrix_t} | {name for name in self._matrix_t if name not in by_column}
+        self._staged = 8 * self._shared_doubles_unconditional(self._data) <= self.STAGE_LIMIT
 
     def _constrain(self, raw: Expr, lower, upper) -> tuple[Expr, Expr | None]:
         """(value, log-Jacobian) of the default transforms: log (``lower`` only), logit-interval (both bounds)"""
@@ -1726,8 +1909,16 @@ class Model:
         if name in self._products:
             return self._dims[name]
         r, c = self.dim(rows), self.dim(cols)
+        if r.size is None and c.size is not None and r.runtime_mul == 1:
+            # the rows are a data dimension (the observations x the right-hand sides of a matrix product): its length follows the
+            # data; no index arrays (an index points into a fixed-size dimension) — its columns are read with column() / pack_columns()
+            d = self._dims[name] = Dim(name, None, runtime_len=r.runtime_len, runtime_div=r.runtime_div, runtime_mul=c.size)
+            d._model = weakref.ref(self)
+            d.factors = (r, c)
+            self._products[name] = (r, c, None, None)
+            return d
         if r.size is None or c.size is None:
-            raise ValueError("a product needs two dimensions of fixed size")
+            raise ValueError("a product needs two dimensions of fixed size (or data rows and fixed-size columns)")
         self.dim(name, r.size * c.size).factors = (r, c)
         e = np.arange(r.size * c.size)
         to_r = self.index(f"{name}_row", e // c.size, dim=name, into=rows)
@@ -1738,6 +1929,8 @@ class Model:
     def reduce(self, expr: Expr, over: str) -> Expr:
         """Sum of a two-dimensional value along the axis ``over``: a vector on the other axis."""
         r, c, to_r, to_c = self._product_of(expr)
+        if to_r is None:
+            raise ValueError(f"{expr.dim.name!r} has data rows: read its columns with column() and sum them")
         if over == r.name:
             return _segsum(expr, to_c)
         if over == c.name:
@@ -1748,6 +1941,8 @@ class Model:
         """A vector on one of the two axes, repeated along the other: a value on the product dimension."""
         self.product(rows, cols)
         r, c, to_r, to_c = self._products[f"{rows}_x_{cols}"]
+        if to_r is None:
+            raise ValueError(f"product({rows!r}, {cols!r}) has data rows: build the value with pack_columns()")
         if vec.dim is r:
             return vec[to_r]
         if vec.dim is c:
@@ -2085,7 +2280,7 @@ class Model:
     def _stage_source(self):
         """``nphip_density_stage`` + the order of the staged fields: doubles first, then the 32-bit integers (each rounded up to a
         whole double)."""
-        fields = [f for f in self._data_fields if f[1] == "double"] + [f for f in self._data_fields if f[1] == "int"]
+        fields = [f for f in self._data_fields if f[1] == "double" and f[0] not in self._unstaged] + [f for f in self._data_fields if f[1] == "int"]
         if not self._staged or not fields:
             return "", fields
         L = ["__device__ void nphip_density_stage(const NphipData& data, double* shared, int thread, int n_threads) {"]
@@ -2108,6 +2303,8 @@ class Model:
             return 0
         total = 0
         for name, kind, _ in self._data_fields:
+            if name in self._unstaged:
+                continue
             if kind == "double":
                 total += len(data[name])
             elif kind == "int":
@@ -2118,7 +2315,7 @@ class Model:
         """-> (source, generator): the HIP source of the density and the object that knows its LDS layout."""
         logp = self.logp_expr()
         grads = gradient(logp, self._params)
-        self._staged = 8 * self._shared_doubles_unconditional(self._data) <= self.STAGE_LIMIT
+        self._plan_staging([logp] + grads + [e for _, e in self._det])
         gen = _Gen(self, logp, grads, waves_per_chain)
         src, _ = gen.source()
         return src, gen
@@ -2141,7 +2338,7 @@ class Model:
             self._data["prof__"] = np.zeros(64)
             self._data_fields.append(("prof__", "raw", None))
         try:
-            self._staged = 8 * self._shared_doubles_unconditional(self._data) <= self.STAGE_LIMIT
+            self._plan_staging([logp] + grads + [e for _, e in self._det])
             gen = _Gen(self, logp, grads, waves_per_chain, profile=True)
             src, _ = gen.source()
             compiled = self._finish(src, gen, waves_per_chain=waves_per_chain)
@@ -2226,7 +2423,7 @@ class Model:
             if waves_per_chain not in (None, 1):
                 raise ValueError("a model with matrix stages (cholesky / solve_lower) runs with waves_per_chain=1")
             waves_per_chain = 1
-        self._staged = 8 * self._shared_doubles_unconditional(self._data) <= self.STAGE_LIMIT
+        self._plan_staging([logp] + grads + [e for _, e in self._det])
         if waves_per_chain is None:
             for waves_per_chain in (1, 2, 4):
                 gen = _Gen(self, logp, grads, waves_per_chain)
@@ -2260,12 +2457,13 @@ class Model:
             return sum(dim_len(d, data) for d in stored_dims)
 
         fields = list(self._data_fields)
-        staged = self._staged and any(k in ("double", "int") for _, k, _ in fields)
+        unstaged = set(self._unstaged)
+        staged = self._staged and any(k in ("double", "int") and n not in unstaged for n, k, _ in fields)
 
         def lds_shared(data):
             if not staged:
                 return 0
-            return sum(len(data[n]) if k == "double" else (len(data[n]) + 1) // 2 for n, k, _ in fields if k in ("double", "int"))
+            return sum(len(data[n]) if k == "double" else (len(data[n]) + 1) // 2 for n, k, _ in fields if k in ("double", "int") and n not in unstaged)
 
         det = list(self._det)
         # the unconstrained values of transformed parameters, under PyMC's names (b_log__, c_zerosum__, d_simplex__ ...): they go to
@@ -2290,7 +2488,8 @@ class Model:
                 return (e.payload[1],)
             if e.dim.name in self._products:
                 r, c, _, _ = self._products[e.dim.name]
-                return (c.size, r.size) if self._det_dims.get(name) == (c.name, r.name) else (r.size, c.size)
+                rs = r.len_py(data)
+                return (c.size, rs) if self._det_dims.get(name) == (c.name, r.name) else (rs, c.size)
             return (e.dim.len_py(data),)
 
         def dims_of(name, e):
@@ -2326,7 +2525,7 @@ class Model:
                     continue
                 if e.dim is not None and e.dim.name in self._products:
                     r, c, _, _ = self._products[e.dim.name]
-                    v = np.asarray(v).reshape(-1, r.size, c.size)
+                    v = np.asarray(v).reshape(np.asarray(v).shape[0], -1, c.size)
                     v = v.transpose(0, 2, 1) if n in transposed else v
                 out[n] = v
             return out
@@ -2353,7 +2552,7 @@ class Model:
         else:
             out_names, out_shapes = names, shapes
         egen = _Gen(self, Expr.const(0.0), [], waves_per_chain, outputs=offs, fn_name="nphip_expand") if (fixed and det) else None
-        if egen is not None and any(n.op in _SCANOPS for n in egen.order):
+        if egen is not None and any(n.op in _SCANOPS + _MVOPS for n in egen.order):
             # (the generated expand keeps its arrays in LDS, (4 rows per workgroup with one wave per row) + the staged data: a long scan
             #  that does not fit is expanded on the host)
             rows_per_block = 4 if waves_per_chain == 1 else 1
@@ -2438,6 +2637,9 @@ def _symbolic_model_class():
                     new[k] = a.reshape(-1)
                     continue
                 new[k] = float(v) if kind == "sdouble" else np.ascontiguousarray(v, dtype=np.int32 if kind == "int" else np.float64)
+            for name in f._matrix_t:      # the transposed copies the stages read
+                K = f._matrix_cols[name]
+                new[name + "__t"] = np.ascontiguousarray(new[name].reshape(-1, K).T).reshape(-1)
             for name in f._indices:
                 f._derive(name, new)
             # arrays of one dimension must keep a common length

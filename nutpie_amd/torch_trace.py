@@ -20,7 +20,9 @@ source element it reads — an identity (nothing to do), a prefix (``trunc``), a
 (``Gather``; its transpose in the gradient is the IR's ``SegSum``).  Reductions along an axis are ``SegSum`` through the map from
 input to output element; ``cat`` is ``pad`` / ``Gather`` under ``where_lt``.  Tensors the function closes over (the model's data)
 are constants of the trace: operations on constants alone are evaluated eagerly, and a constant that meets a traced value
-becomes a data array of the compiled model.
+becomes a data array of the compiled model.  A constant two-dimensional matrix times a traced vector is the IR's design-matrix
+product (``Model.matrix``): unrolled over up to 63 columns, the data-matrix stage of ``csrc/chain_matvec.h`` beyond, and for a
+traced k x R matrix (``X @ B``, up to 16 right-hand sides).
 
 The position vector.  ``x[a:b]`` and ``x[k]`` (also through a leading batch axis of length one) become the model's parameters
 when the pieces do not overlap; any other use of ``x`` makes the whole vector one parameter and the pieces gathers from it.
@@ -412,8 +414,8 @@ class _Interp:
         sa, sb = self.shape_of(a), self.shape_of(b)
         if len(sa) == 0 or len(sb) == 0:
             raise UnsupportedTorchOp("matmul with a zero-dimensional operand")
-        # a data matrix times a traced vector with few columns: the IR's design-matrix form (one wave-wide sum per column in the
-        # gradient); `v @ M` with M[k, n] data is the same product with the transposed matrix
+        # a data matrix times a traced vector: the IR's design-matrix form (few columns: one wave-wide sum per column in the gradient;
+        # many: the data-matrix stage); `v @ M` with M[k, n] data is the same product with the transposed matrix
         if self.is_const(b) and len(sb) == 2 and len(sa) in (1, 2) and _numel(sa) == sb[0] and not self.is_const(a):
             r = self._data_matrix_product(b.t(), a, (sb[1],) if len(sa) == 1 else (1, sb[1]), None)
             if r is not None:
@@ -422,6 +424,15 @@ class _Interp:
             r = self._data_matrix_product(a, b, (sa[0],) if len(sb) == 1 else (sa[0], 1), a)
             if r is not None:
                 return r
+        # a data matrix times a traced k x R matrix (the classes of a softmax regression; leading axes of length one are the batch's):
+        # one product with R right-hand sides, the n x R result row-major as torch has it
+        if (self.is_const(a) and len(sa) >= 2 and len(sb) >= 2 and sb[-2] == sa[-1] and 2 <= sb[-1] <= S.MAX_RHS and _numel(sa[:-2]) == 1
+                and _numel(sb[:-2]) == 1 and sa[-2] > 1 and sa[-1] > 1 and not self.is_const(b) and not (isinstance(b, _X) and not self.whole)):
+            bv = self.sym(b)
+            n, k, R = sa[-2], sa[-1], sb[-1]
+            if bv.expr.dim is not None and bool(torch.isfinite(a).all()):
+                m = self.m.matrix(self.fresh_name(a), a.reshape(n, k).to(torch.float64).contiguous().cpu().numpy(), dim=self.dim(n).name, cols=self.dim(k).name)
+                return _Sym(m.times(bv.expr, self.dim(n * R), R), (1,) * (max(len(sa), len(sb)) - 2) + (n, R))
         av = a if self.is_const(a) else self.sym(a)
         bv = b if self.is_const(b) else self.sym(b)
         a1 = len(sa) == 1
@@ -441,7 +452,9 @@ class _Interp:
     def _data_matrix_product(self, mat, vec, out_shape, original):
         torch = self.torch
         rows, k = int(mat.shape[0]), int(mat.shape[1])
-        if not (1 < k <= 32 and rows > 1) or isinstance(vec, _X) and not self.whole:
+        # (up to Matrix.STAGE_ABOVE columns the IR unrolls the product over the columns; beyond, `Matrix @` is the data-matrix stage
+        #  of csrc/chain_matvec.h: the matrix is read as data, never expanded into an n k-element product)
+        if not (k > 1 and rows > 1) or isinstance(vec, _X) and not self.whole:
             return None
         bv = self.sym(vec)
         if bv.expr.dim is None or not bool(torch.isfinite(mat).all()):
