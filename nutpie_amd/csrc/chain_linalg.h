@@ -9,7 +9,11 @@
 //
 // Summation order: every dot product is ONE accumulator updated by fused multiply-adds in ascending order of
 // its index, starting from the value it is subtracted from (or +0.0).  No atomics and no cross-lane sums: a lane's results
-// depend on its own chain only.
+// depend on its own chain only.  The subtracted products enter as fma(-l, x, s): the sign on the first factor.  Everything else is one
+// IEEE operation per written operation: the pivot's square root, one division per element (no reciprocal), the halving and the
+// fold G[i][j] + G[j][i] of cholesky_adj, the negation AFTER the sum in solve_lower_adj_l (a zero sum gives -0.0 on the triangle).
+// Restated on the CPU as the test oracle's oracle_chain_cholesky, _solve_lower, _solve_lower_t, _solve_lower_adj_l, _cholesky_adj;
+// tests/test_gpu_chain_stages.py holds the five routines to that bit for bit.
 #pragma once
 
 #if defined(NPHIP_JIT_W) && NPHIP_JIT_W != 1

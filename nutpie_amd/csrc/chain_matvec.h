@@ -13,6 +13,8 @@
 // summed index in ascending order — E[i][r] = fma(X[i][c], B[c][r], E[i][r]) for c = 0 .. K-1, C[c][r] = fma(X[i][c], G[i][r],
 // C[c][r]) for i = 0 .. n-1.  No atomics, no sums across lanes, no split of the summed range, nothing from another chain: the result
 // is a function of (n, K, R) and the chain's own inputs, not of W and not of which lane computes it.
+// Restated on the CPU as the test oracle's oracle_chain_times / oracle_chain_times_t; tests/test_gpu_chain_stages.py holds both
+// routines to that bit for bit at W = 1, 2, 4.
 //
 // Issue: a lane keeps several outputs side by side (ROWS row blocks in times; up to COLB column blocks in times_t, a lane with more
 // goes over the rows once per group of COLB) and the loads of several summed indices in flight (the loops are unrolled by COLS

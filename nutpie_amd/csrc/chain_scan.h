@@ -7,15 +7,21 @@
 // (a prefix sum: no multiplier carried).  Called by all 64 W lanes of the chain (W = NPHIP_JIT_W waves, `lane` in [0, 64 W));
 // returns after the chain's barrier: the output is then visible to every lane.  The input arrays are not written.
 //
-// Order contract: a row is cut into segments of 64 W consecutive elements, lane l of the chain holding element
-// s 64 W + l.  Every element is the affine map (A, B): x -> A x + B, past the row's end the identity (1, 0).  In a segment:
+// Order contract (restated on the CPU as the test oracle's oracle_chain_scan, and the routine is held to that
+// bit for bit by tests/test_gpu_chain_stages.py): a row is cut into segments of 64 W consecutive elements, lane l of the chain holding
+// element s 64 W + l.  Every element is the affine map (A, B): x -> A x + B, past the row's end the identity (1, 0) — scanned like any
+// other element (it comes after every stored one).  In a segment:
 //   1. each wave takes the inclusive scan of its 64 maps by the fixed pattern row_shr 1, 2, 4, 8 (within rows of 16 lanes), then
 //      row_bcast 15 (into rows 1, 3) and row_bcast 31 (into rows 2, 3); composing an earlier map (A1, B1) into a later one (A2, B2)
-//      gives (A2 A1, fma(A2, B1, B2)) — with a = 1, B1 + B2 —, a lane that has no partner in a step composes the identity;
-//   2. (W > 1) the wave totals go through LDS and every wave composes the totals of the waves before it in ascending order, from
-//      the identity;
-//   3. the carry (x at the previous segment's last element, the row's x_{-1} for the first segment) goes in last:
-//      x = fma(A_lane, fma(A_waves, carry, B_waves), B_lane).
+//      gives (A2 A1, fma(A2, B1, B2)) — with a = 1, B2 + B1 —; a lane that has no partner in a step composes the identity as the
+//      EARLIER map, (A 1, fma(A, 0.0, B)) resp. B + 0.0.  That is an operation, not a no-op: B = -0.0 becomes +0.0 (unless A < 0), and
+//      a non-finite A makes B NaN;
+//   2. (W > 1) the wave totals go through LDS and every wave composes, from the identity, the totals of the waves before it in
+//      ascending order, each total as the LATER map: P = (1, 0), then P = (A_v A_P, fma(A_v, B_P, B_v)) for v = 0 .. w - 1 (wave 0
+//      keeps the identity), and xin = fma(A_P, carry, B_P) — with a = 1, carry + B_P; in wave 0 that is fma(1.0, carry, 0.0) resp.
+//      carry + 0.0.  With W = 1 there is no such step: xin = carry;
+//   3. the carry (x at the previous segment's last element, lane 64 W - 1; the row's x_{-1} for the first segment) goes in last:
+//      x = fma(A_lane, xin, B_lane) — with a = 1, xin + B_lane.
 // Every operation is a fixed function of (R, T, W) and the chain's own inputs: no atomics, nothing from other chains.  A non-finite
 // input makes the outputs that depend on it non-finite; an explosive |a| > 1 overflows whatever the order (not guarded).
 //

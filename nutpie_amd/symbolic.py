@@ -1107,7 +1107,7 @@ def _np_matop(op: str, args: list[np.ndarray], k: int, m: int) -> np.ndarray:
 
 
 def _np_scan(op: str, args: list[np.ndarray], R: int, T: int, N: int) -> np.ndarray:
-    """the recurrence (``scan``) or its adjoint (``rscan``) by a plain loop over time: the checker, not a bitwise reference"""
+    """the recurrence (``scan``) or its adjoint (``rscan``) by a plain loop over time: the checker (the bitwise reference of the device routine is the CPU oracle's ``oracle_chain_scan``)"""
     def rows(v):
         return np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, R * T)).reshape(N, R, T)
 

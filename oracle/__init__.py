@@ -163,6 +163,8 @@ def lib():
         _lib.oracle_w_add.argtypes = [C.c_double, C.c_int64, C.c_double, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         _lib.oracle_dot.restype = C.c_double
         _lib.oracle_leapfrog_tridiag.restype = C.c_double
+        _lib.oracle_chain_scan.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        _lib.oracle_chain_scan.restype = None
     return _lib
 
 
@@ -387,6 +389,95 @@ def dot(x, y, waves=1):
     x = np.ascontiguousarray(x, dtype=np.float64)
     y = np.ascontiguousarray(y, dtype=np.float64)
     return lib().oracle_dot(_p(x), _p(y), C.c_uint64(x.size), C.c_int(waves))
+
+
+# ---- the stages inside the generated densities (csrc/chain_scan.h, chain_matvec.h, chain_linalg.h), one chain per call
+
+
+def _f64(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    assert shape is None or a.shape == tuple(shape), (a.shape, shape)
+    return a
+
+
+def chain_scan(b, a=1.0, init=0.0, waves=1, rev=False):
+    """x_t = a_t x_{t-1} + b_t along the last axis of ``b[R, T]`` (or ``b[T]``) as ``waves`` waves per chain compute it.  ``a``: an
+    array like ``b``, a float (one coefficient), or the integer 1 (the a = 1 variant: plain additions); ``init``: a float or ``[R]``.
+    ``rev``: the adjoint lambda_t = a_{t+1} lambda_{t+1} + b_t (``init`` is not used)."""
+    b2 = _f64(np.atleast_2d(b))
+    R, T = b2.shape
+    if isinstance(a, (int, np.integer)):
+        assert a == 1
+        kind, arr, a_s = 2, None, 1.0
+    elif np.ndim(a) == 0:
+        kind, arr, a_s = 1, None, float(a)
+    else:
+        kind, arr, a_s = 0, _f64(np.atleast_2d(a), (R, T)), 1.0
+    irow = np.ndim(init) > 0
+    iarr = _f64(init, (R,)) if irow else None
+    x = np.empty_like(b2)
+    lib().oracle_chain_scan(R, T, int(waves), kind, int(bool(rev)), int(irow), _p(arr), a_s, _p(b2), _p(iarr), 0.0 if irow else float(init), _p(x))
+    return x.reshape(np.shape(b))
+
+
+def chain_times(X, B):
+    """E = X B: ``X[n, K]``, ``B[K, R]`` -> ``E[n, R]``."""
+    X, B = _f64(X), _f64(B)
+    (n, K), R = X.shape, B.shape[1]
+    Xt, E = np.ascontiguousarray(X.T), np.empty((n, R))
+    lib().oracle_chain_times(n, K, R, _p(Xt), _p(B), _p(E))
+    return E
+
+
+def chain_times_t(X, G):
+    """C = X^T G: ``X[n, K]``, ``G[n, R]`` -> ``C[K, R]``."""
+    X, G = _f64(X), _f64(G)
+    (n, K), R = X.shape, G.shape[1]
+    Cm = np.empty((K, R))
+    lib().oracle_chain_times_t(n, K, R, _p(X), _p(G), _p(Cm))
+    return Cm
+
+
+def chain_cholesky(A):
+    """(L, ok): the lower triangle of ``A[K, K]`` is read."""
+    A = _f64(A)
+    L = np.empty_like(A)
+    ok = lib().oracle_chain_cholesky(A.shape[0], _p(A), _p(L))
+    return L, bool(ok)
+
+
+def chain_solve_lower(L, B):
+    L, B = _f64(L), _f64(B)
+    X = np.empty_like(B)
+    lib().oracle_chain_solve_lower(L.shape[0], B.shape[1], _p(L), _p(B), _p(X))
+    return X
+
+
+def chain_solve_lower_t(L, G, by_rows=False):
+    """Y = L^-T G on the columns of ``G[K, N]``; ``by_rows``: on the rows of ``G[N, K]`` (the second substitution of ``cholesky_adj``)."""
+    L, G = _f64(L), _f64(G)
+    Y = np.empty_like(G)
+    K = L.shape[0]
+    if by_rows:
+        lib().oracle_chain_solve_lower_t(K, G.shape[0], 1, K, _p(L), _p(G), _p(Y))
+    else:
+        lib().oracle_chain_solve_lower_t(K, G.shape[1], G.shape[1], 1, _p(L), _p(G), _p(Y))
+    return Y
+
+
+def chain_solve_lower_adj_l(Bbar, X):
+    Bbar, X = _f64(Bbar), _f64(X)
+    K, N = X.shape
+    Lbar = np.empty((K, K))
+    lib().oracle_chain_solve_lower_adj_l(K, N, _p(Bbar), _p(X), _p(Lbar))
+    return Lbar
+
+
+def chain_cholesky_adj(L, Lbar):
+    L, Lbar = _f64(L), _f64(Lbar)
+    Abar = np.empty_like(L)
+    lib().oracle_chain_cholesky_adj(L.shape[0], _p(L), _p(Lbar), _p(Abar))
+    return Abar
 
 
 def leapfrog_tridiag(q, p, g, sig2, eps, diag, offdiag=None, mu=None, waves=1):

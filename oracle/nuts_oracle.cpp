@@ -1303,3 +1303,181 @@ int oracle_is_turning(uint64_t dim, const double* sig2, int waves, int64_t idx1,
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// The order contracts of the stages that run inside the generated densities (nutpie_amd/csrc/chain_scan.h, chain_matvec.h,
+// chain_linalg.h), restated from their text: std::fma where the contract names an fma, plain IEEE
+// operations elsewhere.  tests/test_gpu_chain_stages.py compares the device routines with these bit for bit.
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// an element of a scan: the affine map x -> A x + B
+struct Affine { double A, B; };
+const Affine AFFINE_ID = {1.0, 0.0};
+
+// the earlier map composed into the later one (`one`: a = 1 everywhere, no multiplier is carried and the sums are plain additions)
+Affine compose(Affine earlier, Affine later, bool one) {
+    if (one) return {1.0, later.B + earlier.B};
+    return {later.A * earlier.A, std::fma(later.A, earlier.B, later.B)};
+}
+
+// the inclusive scan of one wave's 64 maps by the fixed pattern: every step reads the values of the step before in all lanes
+void wave_scan_pattern(Affine* m, bool one) {
+    Affine old[64];
+    for (int d = 1; d <= 8; d *= 2) {                 // row_shr 1, 2, 4, 8 within rows of 16 lanes
+        memcpy(old, m, sizeof(old));
+        for (int l = 0; l < 64; ++l) m[l] = compose((l % 16) >= d ? old[l - d] : AFFINE_ID, old[l], one);
+    }
+    memcpy(old, m, sizeof(old));                        // row_bcast 15: the last lane of rows 0 and 2 into rows 1 and 3
+    for (int l = 0; l < 64; ++l) {
+        const int row = l / 16;
+        m[l] = compose(row % 2 == 1 ? old[16 * row - 1] : AFFINE_ID, old[l], one);
+    }
+    memcpy(old, m, sizeof(old));                        // row_bcast 31: lane 31 into rows 2 and 3
+    for (int l = 0; l < 64; ++l) m[l] = compose(l >= 32 ? old[31] : AFFINE_ID, old[l], one);
+}
+
+// one forward row: a (nullptr: the scalar a_s, or 1 when `one`), b, x of T elements, x_{-1} = init
+void scan_row(int T, int W, bool one, const double* a, double a_s, const double* b, double init, double* x) {
+    const int SEG = 64 * W;
+    double carry = init;
+    std::vector<Affine> seg(SEG);
+    for (int s0 = 0; s0 < T; s0 += SEG) {
+        for (int l = 0; l < SEG; ++l) {
+            const int t = s0 + l;
+            seg[l] = t < T ? Affine{one ? 1.0 : (a ? a[t] : a_s), b[t]} : AFFINE_ID;
+        }
+        for (int w = 0; w < W; ++w) wave_scan_pattern(&seg[64 * w], one);
+        double last = carry;
+        for (int w = 0; w < W; ++w) {
+            double xin = carry;
+            if (W > 1) {   // the totals of the waves before this one, ascending from the identity; then the carry
+                Affine before = AFFINE_ID;
+                for (int v = 0; v < w; ++v) before = compose(before, seg[64 * v + 63], one);
+                xin = one ? carry + before.B : std::fma(before.A, carry, before.B);
+            }
+            for (int l = 0; l < 64; ++l) {
+                const Affine e = seg[64 * w + l];
+                const double xv = one ? xin + e.B : std::fma(e.A, xin, e.B);
+                if (s0 + 64 * w + l < T) x[s0 + 64 * w + l] = xv;
+                if (w == W - 1 && l == 63) last = xv;
+            }
+        }
+        carry = last;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+void oracle_chain_scan(int R, int T, int W, int a_kind, int rev, int init_per_row, const double* a, double a_s, const double* b,
+                       const double* init, double i_s, double* x) {
+    const bool one = a_kind == 2;
+    std::vector<double> ar(T), br(T), xr(T);
+    for (int r = 0; r < R; ++r) {
+        const double* arow = a_kind == 0 ? a + (size_t)r * T : nullptr;
+        const double* brow = b + (size_t)r * T;
+        double* xrow = x + (size_t)r * T;
+        if (!rev) {
+            scan_row(T, W, one, arow, a_s, brow, init_per_row ? init[r] : i_s, xrow);
+            continue;
+        }
+        // the adjoint: the same routine on the reversed row, the coefficients shifted by one (a_{t+1} multiplies lambda_{t+1}; the first
+        // reversed element has nothing before it: coefficient 0), x_{-1} = 0
+        for (int t = 0; t < T; ++t) {
+            br[t] = brow[T - 1 - t];
+            ar[t] = t == 0 ? 0.0 : (a_kind == 0 ? arow[T - t] : a_s);
+        }
+        scan_row(T, W, one, one ? nullptr : ar.data(), a_s, br.data(), 0.0, xr.data());
+        for (int t = 0; t < T; ++t) xrow[T - 1 - t] = xr[t];
+    }
+}
+
+// E = X B with X given transposed (Xt[c n + i]); B K x R, E n x R
+void oracle_chain_times(int n, int K, int R, const double* Xt, const double* B, double* E) {
+    for (int i = 0; i < n; ++i)
+        for (int r = 0; r < R; ++r) {
+            double acc = 0.0;
+            for (int c = 0; c < K; ++c) acc = std::fma(Xt[(size_t)c * n + i], B[c * R + r], acc);
+            E[(size_t)i * R + r] = acc;
+        }
+}
+
+// C = X^T G with X row-major (X[i K + c]); G n x R, C K x R
+void oracle_chain_times_t(int n, int K, int R, const double* X, const double* G, double* C) {
+    for (int c = 0; c < K; ++c)
+        for (int r = 0; r < R; ++r) {
+            double acc = 0.0;
+            for (int i = 0; i < n; ++i) acc = std::fma(X[(size_t)i * K + c], G[(size_t)i * R + r], acc);
+            C[c * R + r] = acc;
+        }
+}
+
+int oracle_chain_cholesky(int K, const double* A, double* L) {
+    for (int e = 0; e < K * K; ++e) L[e] = 0.0;
+    for (int j = 0; j < K; ++j) {
+        double pivot = A[j * K + j];
+        for (int k = 0; k < j; ++k) pivot = std::fma(-L[j * K + k], L[j * K + k], pivot);
+        if (!(pivot > 0.0) || !(pivot < INFINITY)) {
+            for (int e = 0; e < K * K; ++e) L[e] = NAN;
+            return 0;
+        }
+        const double root = std::sqrt(pivot);
+        L[j * K + j] = root;
+        for (int i = j + 1; i < K; ++i) {
+            double s = A[i * K + j];
+            for (int k = 0; k < j; ++k) s = std::fma(-L[i * K + k], L[j * K + k], s);
+            L[i * K + j] = s / root;
+        }
+    }
+    return 1;
+}
+
+void oracle_chain_solve_lower(int K, int N, const double* L, const double* B, double* X) {
+    for (int c = 0; c < N; ++c)
+        for (int i = 0; i < K; ++i) {
+            double s = B[i * N + c];
+            for (int k = 0; k < i; ++k) s = std::fma(-L[i * K + k], X[k * N + c], s);
+            X[i * N + c] = s / L[i * K + i];
+        }
+}
+
+// element (i, c) of G and Y at i rs + c cs; G and Y may be the same array
+void oracle_chain_solve_lower_t(int K, int N, int rs, int cs, const double* L, const double* G, double* Y) {
+    for (int c = 0; c < N; ++c)
+        for (int i = K - 1; i >= 0; --i) {
+            double s = G[i * rs + c * cs];
+            for (int k = i + 1; k < K; ++k) s = std::fma(-L[k * K + i], Y[k * rs + c * cs], s);
+            Y[i * rs + c * cs] = s / L[i * K + i];
+        }
+}
+
+void oracle_chain_solve_lower_adj_l(int K, int N, const double* Bbar, const double* X, double* Lbar) {
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j < K; ++j) {
+            double s = 0.0;
+            if (j <= i) {
+                for (int c = 0; c < N; ++c) s = std::fma(Bbar[i * N + c], X[j * N + c], s);
+                s = -s;
+            }
+            Lbar[i * K + j] = s;
+        }
+}
+
+void oracle_chain_cholesky_adj(int K, const double* L, const double* Lbar, double* Abar) {
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double s = 0.0;
+            for (int k = i; k < K; ++k) s = std::fma(L[k * K + i], Lbar[k * K + j], s);
+            Abar[i * K + j] = Abar[j * K + i] = 0.5 * s;
+        }
+    oracle_chain_solve_lower_t(K, K, K, 1, L, Abar, Abar);   // L^-T P: the columns
+    oracle_chain_solve_lower_t(K, K, 1, K, L, Abar, Abar);   // (L^-T P) L^-1: the rows
+    for (int i = 0; i < K; ++i)
+        for (int j = 0; j < i; ++j) Abar[i * K + j] = Abar[i * K + j] + Abar[j * K + i];
+    for (int i = 0; i < K; ++i)
+        for (int j = i + 1; j < K; ++j) Abar[i * K + j] = 0.0;
+}
+
+}  // extern "C"

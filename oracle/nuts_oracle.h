@@ -221,6 +221,23 @@ void oracle_lr_velocity(uint64_t dim, int k, const double* sig2, const double* V
 int oracle_is_turning(uint64_t dim, const double* sig2, int waves, int64_t idx1, const double* p1,
                       const double* psum1, int64_t idx2, const double* p2, const double* psum2);
 
+/* ---- the order contracts of the stages inside the generated densities (nutpie_amd/csrc/chain_scan.h, chain_matvec.h, chain_linalg.h;
+ * DESIGN.md 11.5-11.7), restated from their text; the device routines are compared with these bit for bit ---- */
+/* x_t = a_t x_{t-1} + b_t on R rows of T elements as W waves per chain compute it.  a_kind: 0 an array a[R T], 1 the scalar a_s, 2 the
+ * constant 1 (plain additions).  rev: the adjoint lambda_t = a_{t+1} lambda_{t+1} + b_t.  init[R] when init_per_row, else i_s. */
+void oracle_chain_scan(int R, int T, int W, int a_kind, int rev, int init_per_row, const double* a, double a_s, const double* b,
+                       const double* init, double i_s, double* x);
+/* E[n][R] = X B (Xt[K][n] the transposed matrix, B[K][R]);  C[K][R] = X^T G (X[n][K], G[n][R]) */
+void oracle_chain_times(int n, int K, int R, const double* Xt, const double* B, double* E);
+void oracle_chain_times_t(int n, int K, int R, const double* X, const double* G, double* C);
+/* K x K row-major.  cholesky: returns 1, or 0 with all of L NaN when a pivot is not positive and finite; the upper triangle is +0.0 */
+int oracle_chain_cholesky(int K, const double* A, double* L);
+void oracle_chain_solve_lower(int K, int N, const double* L, const double* B, double* X);
+/* Y = L^-T G on a block whose element (i, c) is at i rs + c cs (G and Y may be the same array) */
+void oracle_chain_solve_lower_t(int K, int N, int rs, int cs, const double* L, const double* G, double* Y);
+void oracle_chain_solve_lower_adj_l(int K, int N, const double* Bbar, const double* X, double* Lbar);
+void oracle_chain_cholesky_adj(int K, const double* L, const double* Lbar, double* Abar);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,12 @@ def main():
         keep.add(compile_pymc_model(make()).library_path())
     cm = symbolic_models.radon().compile(waves_per_chain=2)   # tests/test_gpu_density.py: the metric with two waves per chain
     keep.update((cm.library_path(), cm.library_path(low_rank=True)))
+    # the probe densities that reach the chain stages directly (tests/test_gpu_chain_stages.py)
+    import chain_stage_probes
+
+    for family, W in chain_stage_probes.PROBES:
+        keep.add(chain_stage_probes.probe(family, W).model.library_path())
+    keep.add(chain_stage_probes.expand_probe()[0].library_path())
     # Libraries of EARLIER engine sources (the cache key hashes the engine's sources: nothing of this tree can find them any more) are removed —
     # only files older than the engine library this tree has just built, so that a model another process is compiling right now, or a user's
     # own models compiled against this engine, are left alone.
