@@ -355,6 +355,10 @@ int nphip_test_dot(int device, int waves, uint64_t n, const double* x, const dou
 /* host-only: the evaluation pool of the host-callback path (spin-waiting workers, `use` threads per batch); row r of batch b
  * adds (b + 1) * (r + 1) into out[r]; *usable_cores = the core count the pool is sized against (affinity and cgroup quota) */
 int nphip_test_rowpool(int threads, uint64_t rows, int batches, int use, uint64_t* out, int* usable_cores);
+/* host-only: the job geometry the engine chooses (waves per chain, kernel family, chunks per wave, padded row length, ...; host.hip:
+ * choose_geometry) and whether the table of kernel families (csrc/kernel_families.h) has that instantiation */
+int nphip_test_choose_geometry(int kind, int dense, uint64_t dim, int waves_per_chain, int jit_w, int jit_nv, int low_rank_metric, int no_register_kernel,
+                               int no_stream_cache, int64_t* out, char* family_name);
 
 #ifdef __cplusplus
 }

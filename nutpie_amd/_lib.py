@@ -91,7 +91,7 @@ _lib_lock = threading.Lock()
 
 def build(force: bool = False) -> str:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("kernels.hip", "host.hip", "linalg.hip", "lowrank_est.hip", "engine_types.h", "dense_tile.h", "Makefile")]
+    srcs = [os.path.join(_CSRC, f) for f in ("kernels.hip", "host.hip", "linalg.hip", "lowrank_est.hip", "engine_types.h", "kernel_families.h", "dense_tile.h", "Makefile")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("nutpie_hip.h", "nphip_spec.h")]
     stale = not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -201,6 +201,7 @@ def lib():
             L.nphip_test_detmath.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]
             L.nphip_test_dot.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
             L.nphip_test_rowpool.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+            L.nphip_test_choose_geometry.argtypes = [C.c_int, C.c_int, C.c_uint64] + [C.c_int] * 6 + [C.POINTER(C.c_int64), C.c_char_p]
             _lib = L
     return _lib
 
@@ -1033,6 +1034,21 @@ def test_rowpool(threads, rows, batches, use=0):
     if lib().nphip_test_rowpool(int(threads), C.c_uint64(int(rows)), int(batches), int(use), out.ctypes.data_as(C.c_void_p), C.byref(cores)) != NPHIP_OK:
         raise RuntimeError(_err())
     return out, int(cores.value)
+
+
+def test_choose_geometry(dim, *, kind=0, dense=False, waves_per_chain=0, jit_w=0, jit_nv=0, low_rank_metric=False, no_register_kernel=False,
+                         no_stream_cache=False):
+    """Host-only: the geometry the engine gives a job (host.hip: choose_geometry).  ``kind``: 0 fused, 1 host callback, 2 device
+    callback, 3 compiled density.  ``in_table``: the table of kernel families has the chosen (family, W, NV)."""
+    out = (C.c_int64 * 9)()
+    name = C.create_string_buffer(16)
+    if lib().nphip_test_choose_geometry(int(kind), int(bool(dense)), C.c_uint64(int(dim)), int(waves_per_chain), int(jit_w), int(jit_nv), int(bool(low_rank_metric)),
+                                        int(bool(no_register_kernel)), int(bool(no_stream_cache)), out, name) != NPHIP_OK:
+        raise RuntimeError(_err())
+    keys = ("W", "family_id", "NV", "ld", "lean", "stream_cache", "sig_lds", "no_register_kernel", "in_table")
+    g = {k: (int(v) if k in ("W", "family_id", "NV", "ld") else bool(v)) for k, v in zip(keys, out)}
+    g["family"] = name.value.decode()
+    return g
 
 
 def test_detmath(fn: str, x, device=0):

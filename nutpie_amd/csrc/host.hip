@@ -26,6 +26,7 @@
 #include "../../include/nutpie_hip.h"
 #include "../../include/nphip_spec.h"
 #include "engine_types.h"
+#include "kernel_families.h"
 
 namespace nphip {
 hipError_t launch_advance(const Args& a, const Args* d_args, bool fused, int W, hipStream_t st, const LaunchSlice* slice = nullptr);
@@ -789,36 +790,84 @@ struct nphip_sampler {
     }
 };
 
-// Waves per chain: a function of the dimension ONLY.  The summation geometry (hence every float of a chain) depends on
-// it, and a chain's result must not depend on how many other chains run with it or on how they are sharded.  (Measured:
-// with 64..256 chains at D = 1000, waves_per_chain = 4 is 20 % faster — available through nphip_launch_t, not chosen
-// behind the user's back; 2 waves per chain are slower than 1.)
 // Leapfrogs per chain per launch of a fused model: about 10 ms of kernel.  A launch boundary costs every chain a flush and a
 // reload of its on-chip state, and the device the tail of the chain that met the most draw ends (measured, bench.py: D = 1000
 // 201 / 208 / 210 / 213 M leapfrogs/s with 256 / 512 / 1024 / 2048 per launch; D = 10 000 10.6 / 12.2 / 13.0 with 32 / 128 / 512
 // and nothing beyond).  Results do not depend on it.
 static int default_evals_per_launch(uint64_t dim) { return dim <= 1024 ? 2048 : (dim <= 4096 ? 1024 : 512); }
 
-static int choose_waves(uint64_t dim) {
-    if (dim <= 1024) return 1;
-    if (dim <= 2048) return 2;
-    // 2048 < D <= 4096: register kernels with the LDS ring; 4096 < D <= 10240: lean register kernels, state in VGPRs + AGPRs.
-    // Measured (profiles/r2_grid_b_lean_w8_vs_w4.txt, 1024 chains): 4 waves per chain beat 8 from D = 7000 up (10.2 vs 6.9 M
-    // leapfrogs/s at D = 10 000: at 8 waves the 256-VGPR budget spills the state) and tie below.
-    // 10240 < D <= 12288 (round 6): the same kernels with 21 .. 24 chunks per wave — they spill, and run 1.3 - 1.6 x the memory-resident ones
-    if (dim <= 12288) return 4;
-    return 8;  // memory-resident kernels; measured at D = 10 000: W = 8 (5.5 M leapfrogs/s) beats 4 (5.0) and 16 (3.6)
-}
-
-// Device-callback models run on the launch-per-evaluation kernels, whose fused leaf holds up to two chunks of 128 dimensions per
-// wave in registers (kernels.hip: leaf_cb, NPHIP_CB_CHUNKS): the fewest waves per chain that keep a row inside it — a function of
-// the dimension alone, like choose_waves (a chain's floats depend on the number of waves that sum over its row).  Measured at
-// D = 1000 x 1024 chains (profiles/r4_callback_kernels.txt): 4 waves x 2 chunks 33.5 us per launch, 2 waves x 4 chunks 36.6.
-static int choose_waves_callback(uint64_t dim) {
-    const uint64_t nch = (dim + 127) / 128;
-    for (int w = 1; w <= 16; w *= 2)
-        if (nch <= 2u * (uint64_t)w) return w;
-    return 16;
+// The geometry of a job — waves per chain, kernel family, chunks per wave, padded row length — as a pure function of the model and
+// what the caller asked for; every range in it is read from the table of families (kernel_families.h).
+//
+// Waves per chain are a function of the dimension ONLY: the summation geometry (hence every float of a chain) depends on them, and a
+// chain's result must not depend on how many other chains run with it or on how they are sharded.  (Measured: with 64..256 chains at
+// D = 1000, waves_per_chain = 4 is 20 % faster — available through nphip_launch_t, not chosen behind the user's back; 2 waves per
+// chain are slower than 1.)
+struct GeometryIn {
+    int kind = 0;             // 0 fused, 1 host callback, 2 device callback, 3 runtime-compiled density
+    bool dense = false;
+    uint64_t dim = 0;
+    int waves_per_chain = 0;  // 0: by dimension
+    int jit_w = 0, jit_nv = 0;
+    bool low_rank_metric = false, no_register_kernel = false, no_stream_cache = false;
+};
+struct Geometry {
+    int W = 0;
+    Family family = Family::memory;
+    int reg_nv = 0;           // Args::reg_nv: chunks per wave held in registers (0: none)
+    int kernel_nv = 0;        // the NV of the k_advance this launches (the memory-resident forms: 0, -1 under the low-rank metric, -8 cached)
+    bool lean = false;
+    int64_t ld = 0;
+    bool stream_cache = false, sig_lds = false;
+    bool no_register_kernel = false;   // as asked for, or because the low-rank metric has no register kernel of this geometry
+};
+static Geometry choose_geometry(const GeometryIn& in) {
+    Geometry g;
+    const int64_t chunks = (int64_t)((in.dim + 127) / 128);
+    const bool fused = in.kind == 0, dens = in.kind == 3, lrm = in.low_rank_metric;
+    if (dens) g.W = in.jit_w;
+    else if (in.waves_per_chain) g.W = in.waves_per_chain;
+    else if (in.kind == 2 && !(in.dense && has(kDenseResident, 1, chunks))) {
+        // Device-callback models run on the launch-per-evaluation kernels, whose fused leaf holds up to two chunks of 128 dimensions per
+        // wave in registers (kernels.hip: leaf_cb, NPHIP_CB_CHUNKS): the fewest waves per chain that keep a row inside it.  Measured at
+        // D = 1000 x 1024 chains (profiles/r4_callback_kernels.txt): 4 waves x 2 chunks 33.5 us per launch, 2 waves x 4 chunks 36.6.
+        // (the dense Gaussian up to 1024 dimensions: one wave per chain — the geometry of its resident kernel, whichever form runs)
+        g.W = 1;
+        while (g.W < kMaxWaves && chunks > 2 * g.W) g.W *= 2;
+    } else {
+        // one wave per chain, then two / four with the LDS ring (1024 < D <= 4096), then the lean kernels with the state in VGPRs + AGPRs.
+        // Measured (profiles/r2_grid_b_lean_w8_vs_w4.txt, 1024 chains): 4 waves per chain beat 8 from D = 7000 up (10.2 vs 6.9 M
+        // leapfrogs/s at D = 10 000: at 8 waves the 256-VGPR budget spills the state) and tie below.  10240 < D <= 12288 (round 6): the
+        // same kernels with 21 .. 24 chunks per wave — they spill, and run 1.3 - 1.6 x the memory-resident ones that take everything beyond
+        g.W = chunks <= kW1.nv_hi ? 1 : (chunks <= 2 * kRing.nv_hi ? 2 : (chunks <= 4 * kLean4.nv_hi ? 4 : kMemoryWaves));
+    }
+    const int W = g.W;
+    g.ld = chunks * 128;
+    g.no_register_kernel = in.no_register_kernel;
+    if (!(W == 1 || W == 2 || W == 4 || W == 8 || W == 16)) return g;   // (setup() refuses it)
+    const int64_t per_wave = (chunks + W - 1) / W;
+    // (P-slots carry the velocity as a third vector.  Round 4: fused models keep the register-resident leaf under the metric
+    //  (kernels.hip: Machine<..., LR>) in the geometries the default picks up to D = 4096; everything else runs the memory-resident kernels)
+    if (lrm && !dens && !(fused && (has(kW1Lr, W, per_wave) || has(kRingLr, W, per_wave)))) g.no_register_kernel = true;
+    // Register-resident kernels with several waves per chain: every wave owns the same number of chunks, so the leading dimension is
+    // padded to a multiple of 128 * W (pads are exact zeros in every reduction).  One wave per chain: one instantiation per exact chunk
+    // count (straight-line code).  (store_divergences does not change the choice: the register kernels rebuild the pre-step state of a
+    // failed leapfrog in the rare path — kernels.hip: replay_divergence)
+    if (fused && !g.no_register_kernel) {
+        for (const KernelFamily* f : {&kW1One, &kW1, &kRing, &kLean4, &kLean8})
+            if (has(*f, W, per_wave)) { g.family = lrm ? (W == 1 ? Family::w1_lr : Family::ring_lr) : f->family; g.reg_nv = (int)per_wave; g.lean = f->lean; }
+    }
+    // host-callback models and compiled densities with several waves per chain: the same padding, so that resident launches can run them
+    // on the register-resident leaf
+    if (g.reg_nv || ((in.kind == 1 || dens) && has(kRemoteWn, W, per_wave))) g.ld = per_wave * W * 128;
+    // memory-resident fused kernel, one wave per chain (no_register_kernel): cache the cursor's (sigma^2, grad, p, rho) in VGPRs
+    // between leaves.  With more waves per chain the cache costs occupancy (measured).
+    g.stream_cache = fused && !g.reg_nv && has(kMemoryCached, W, kMemoryCached.nv_lo) && !in.no_stream_cache && chunks <= -kMemoryCached.nv_lo && !lrm;
+    // D > 4096 (one chain per CU): sigma^2 of the chain in LDS instead of one more HBM stream per pass
+    g.sig_lds = fused && !g.reg_nv && W >= 8 && g.ld * 8 <= 128 * 1024 && !in.no_stream_cache;
+    if (dens) g.reg_nv = in.jit_nv;
+    g.kernel_nv = g.reg_nv ? g.reg_nv : (g.stream_cache ? kMemoryCached.nv_lo : (lrm ? -1 : 0));
+    return g;
 }
 
 bool nphip_sampler::setup() {
@@ -830,22 +879,19 @@ bool nphip_sampler::setup() {
     T = set.num_tune + set.num_draws;
     fused = model.kind == 0;
     dens = model.kind == 3;
-    // (the dense Gaussian up to 1024 dimensions: one wave per chain — the geometry of its resident kernel, whichever form runs)
-    W = dens ? model.jit_w : (launch.waves_per_chain ? launch.waves_per_chain : (model.kind == 2 && !(model.dense && dim <= 1024) ? choose_waves_callback(dim) : choose_waves(dim)));
     const bool lrm = set.low_rank_metric;
+    GeometryIn gin;
+    gin.kind = model.kind; gin.dense = model.dense; gin.dim = dim; gin.waves_per_chain = launch.waves_per_chain;
+    gin.jit_w = model.jit_w; gin.jit_nv = model.jit_nv;
+    gin.low_rank_metric = lrm; gin.no_register_kernel = launch.no_register_kernel != 0; gin.no_stream_cache = launch.no_stream_cache != 0;
+    const Geometry geo = choose_geometry(gin);
+    W = geo.W;
     if (dens && lrm != model.jit_lr) {
         set_error(lrm ? "this library's resident kernel was not built for the low-rank metric (compile it with -DNPHIP_JIT_LR=1 and say so with nphip_model_jit_low_rank), or use its batched device callback"
                       : "this library's resident kernel was built for the low-rank metric: the job must set low_rank_metric");
         return false;
     }
-    // (P-slots carry the velocity as a third vector.  Round 4: fused models keep the register-resident leaf under the metric
-    //  (kernels.hip: Machine<..., LR>) in the geometries choose_waves() picks up to D = 4096 — one wave per chain, or two / four
-    //  with 5..8 chunks per wave; everything else runs the memory-resident kernels)
-    if (lrm && !dens) {
-        const uint64_t per_wave = ((dim + 127) / 128 + (uint64_t)W - 1) / (uint64_t)W;
-        const bool lr_reg = model.kind == 0 && ((W == 1 && dim <= 1024) || ((W == 2 || W == 4) && per_wave >= 5 && per_wave <= 8));
-        if (!lr_reg) launch.no_register_kernel = 1;
-    }
+    if (geo.no_register_kernel) launch.no_register_kernel = 1;
     if (dens && set.store_divergences) {
         set_error("store_divergences needs the pre-step state in memory: use the batched device callback of the density's library (launch per evaluation)");
         return false;
@@ -897,52 +943,19 @@ bool nphip_sampler::setup() {
     args.n_chains = (int64_t)n;
     args.chain_offset = (int64_t)launch.chain_offset;
     args.dim = (int64_t)dim;
-    args.ld = (int64_t)((dim + 127) / 128 * 128);
-    // register-resident kernels with several waves per chain (1024 < D <= 4096): every wave owns the same number of
-    // chunks, so the leading dimension is padded to a multiple of 128 * W (pads are exact zeros in every reduction)
-    const bool fused_model = (model.kind == 0);
-    int reg_multi = 0;
-    if (fused_model && (W == 2 || W == 4) && !launch.no_register_kernel) {
-        const int64_t per_wave = ((int64_t)((dim + 127) / 128) + W - 1) / W;
-        if (per_wave >= 1 && per_wave <= 8) { reg_multi = (int)per_wave; args.ld = per_wave * W * 128; }
-    }
-    // lean register-resident kernels (8 waves per chain, up to 10 chunks per wave: D <= 10240 — the rows of config 5): state in
-    // VGPRs, sigma^2 in LDS, merge operands streamed (kernels.hip: leaf_lean).  Same padding rule as above.
-    int lean_nc = 0;
-    if (fused_model && (W == 8 || W == 4) && !launch.no_register_kernel) {
-        const int64_t per_wave = ((int64_t)((dim + 127) / 128) + W - 1) / W;
-        if (W == 8 && per_wave >= 1 && per_wave <= 10) { lean_nc = (int)per_wave; args.ld = per_wave * W * 128; }
-        // (experimental geometry: 4 waves per chain with the state spread over VGPRs + AGPRs, one wave per SIMD)
-        if (W == 4 && per_wave > 8 && per_wave <= 24) { lean_nc = (int)per_wave; args.ld = per_wave * W * 128; }   // (21 .. 24, round 6: the build spills and still beats the memory-resident kernels)
-    }
-    // host-callback models with several waves per chain (1024 < D <= 4096): the same padding, so that resident launches can
-    // run them on the register-resident leaf (8 chunks per wave at most)
-    if ((model.kind == 1 || model.kind == 3) && (W == 2 || W == 4)) {
-        const int64_t per_wave = ((int64_t)((dim + 127) / 128) + W - 1) / W;
-        if (per_wave >= 1 && per_wave <= 8) args.ld = per_wave * W * 128;
-    }
+    args.ld = geo.ld;
     args.cap = (int32_t)set.maxdepth;
     args.npslots = num_pslots(args.cap);
     args.nqpool = num_qpool(args.cap);
     const size_t ld = (size_t)args.ld;
-    // register-resident specialisation, one wave per chain: state in VGPRs (dim <= 1024, one instantiation per chunk count)
-    args.reg_nv = lean_nc ? lean_nc : reg_multi;
-    args.lean = lean_nc ? 1 : 0;
-    // (store_divergences does not change the choice: the register kernels rebuild the pre-step state of a failed leapfrog in
-    //  the rare path — kernels.hip: replay_divergence)
-    if (fused && W == 1 && !launch.no_register_kernel) {
-        const int nchunks = (int)(args.ld / 128);  // one kernel instantiation per exact chunk count (straight-line code)
-        if (nchunks <= 8 || (getenv("NPHIP_DEV_W1_WIDE") && nchunks <= 12)) args.reg_nv = nchunks;   // (9 .. 12: developer libraries only, kernels.hip: Machine::NORING)
-    }
-    // memory-resident fused kernel, one wave per chain (store_divergences, no_register_kernel): cache the cursor's
-    // (sigma^2, grad, p, rho) in VGPRs between leaves.  With more waves per chain the cache costs occupancy (measured).
-    args.stream_cache = (fused && !args.reg_nv && W == 1 && !launch.no_stream_cache && args.ld / 128 <= 8 && !lrm) ? 1 : 0;
+    args.reg_nv = geo.reg_nv;
+    args.lean = geo.lean ? 1 : 0;
+    args.stream_cache = geo.stream_cache ? 1 : 0;
     args.pvec = lrm ? 3 : 2;
     args.lr_on = lrm ? 1 : 0;
     s.low_rank_metric = lrm ? 1 : 0;
 
-    // D > 4096 (one chain per CU): sigma^2 of the chain in LDS instead of one more HBM stream per pass
-    args.sig_lds = (fused && !args.reg_nv && W >= 8 && args.ld * 8 <= 128 * 1024 && !launch.no_stream_cache) ? 1 : 0;
+    args.sig_lds = geo.sig_lds ? 1 : 0;
 
     if (!dalloc(&args.ctl, n)) return false;
     if (!dalloc(&args.qpool, n * args.nqpool * 2 * ld)) return false;
@@ -984,7 +997,6 @@ bool nphip_sampler::setup() {
             args.dens_data = model.jit_data;
             args.dens_lds_doubles = (int32_t)(model.jit_lds_bytes / 8);
             args.dens_shared_doubles = (int32_t)(model.jit_shared_bytes / 8);
-            args.reg_nv = model.jit_nv;
             if ((int64_t)model.jit_nv * 128 * W != args.ld) { set_error("the density's library was compiled for another dimension (nv chunks)"); return false; }
         }
         if (model.kind == 1) {
@@ -1019,7 +1031,7 @@ bool nphip_sampler::setup() {
                 remote_nv = (int)(args.ld / 128 / W);
                 // (above 4 MB of positions per step the job is bound by PCIe traffic either way, and launches per evaluation were 15 %
                 //  faster at 1024 chains x 1000 dimensions: resident only when asked for)
-                remote = (W == 1 || W == 2 || W == 4) && remote_nv <= 8 && (int64_t)remote_nv * W * 128 == args.ld && n * (uint64_t)W <= 1024 &&
+                remote = (has(kRemoteW1, W, remote_nv) || has(kRemoteWn, W, remote_nv)) && (int64_t)remote_nv * W * 128 == args.ld && n * (uint64_t)W <= 1024 &&
                          launch.host_persist != 1 && !launch.no_register_kernel && !lrm &&
                          !set.store_divergences && set.pause_draws.empty() && (n * dim * 8 <= (4u << 20) || launch.host_persist > 1);
                 persist_evals = launch.host_persist > 1 ? launch.host_persist : 256;
@@ -1080,7 +1092,7 @@ bool nphip_sampler::setup() {
         // 1.59 against 1.39).  launch.host_persist > 1 forces the resident form.
         const uint64_t wgs_per_die = std::max<uint64_t>(1, ((n + 3) / 4) / 8), n_tiles = (dim + 63) / 64;
         const uint64_t tiles_per_member = (n_tiles + std::min<uint64_t>(16, wgs_per_die) - 1) / std::min<uint64_t>(16, wgs_per_die);
-        dg = W == 1 && dim <= 1024 && (n + 3) / 4 <= (uint64_t)cus && !lrm && !set.store_divergences &&
+        dg = has(kDenseResident, W, args.ld / 128) && (n + 3) / 4 <= (uint64_t)cus && !lrm && !set.store_divergences &&
              set.pause_draws.empty() && !launch.no_register_kernel && launch.host_persist != 1 && launch.host_groups < 2 &&
              (tiles_per_member <= 2 || launch.host_persist > 1);
         if (dg) {
@@ -2341,6 +2353,23 @@ int nphip_test_rowpool(int threads, uint64_t rows, int batches, int use, uint64_
         pool.run(rows, f, use);
         if ((b % 7) == 3) std::this_thread::sleep_for(std::chrono::microseconds(600));   // lets the workers fall asleep in between
     }
+    return NPHIP_OK;
+}
+
+// Host-side test hook (no GPU involved): the geometry choose_geometry() gives a job.  out[0..8] = W, family, kernel NV, padded row
+// length, lean, stream_cache, sig_lds, register kernel ruled out, and whether (family, W, NV) is an instantiation the table of
+// families has; the family's name goes to name[16].
+int nphip_test_choose_geometry(int kind, int dense, uint64_t dim, int waves_per_chain, int jit_w, int jit_nv, int low_rank_metric, int no_register_kernel,
+                               int no_stream_cache, int64_t* out, char* name) {
+    GeometryIn in;
+    in.kind = kind; in.dense = dense != 0; in.dim = dim; in.waves_per_chain = waves_per_chain; in.jit_w = jit_w; in.jit_nv = jit_nv;
+    in.low_rank_metric = low_rank_metric != 0; in.no_register_kernel = no_register_kernel != 0; in.no_stream_cache = no_stream_cache != 0;
+    const Geometry g = choose_geometry(in);
+    bool in_table = false;
+    for (const KernelFamily& f : kFamilies) in_table = in_table || (f.family == g.family && has(f, g.W, g.kernel_nv));
+    const int64_t v[9] = {g.W, (int64_t)g.family, g.kernel_nv, g.ld, g.lean, g.stream_cache, g.sig_lds, g.no_register_kernel, in_table};
+    std::copy(v, v + 9, out);
+    snprintf(name, 16, "%s", kFamilyNames[(int)g.family]);
     return NPHIP_OK;
 }
 

@@ -20,6 +20,7 @@
 
 #include "../../include/nphip_spec.h"
 #include "engine_types.h"
+#include "kernel_families.h"
 
 // address-space qualifiers only exist in the device pass (the host pass merely parses the kernels)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -63,33 +64,6 @@ template <int W>
 // lean kernels: the unrolled chunk sweeps must stay sweeps — without a fence per chunk the scheduler issues the loads of
 // all chunks first and the allocator spills the resident state to make room for them
 #define NPHIP_CHUNK_FENCE(k) __builtin_amdgcn_sched_barrier(0)
-// one wave per chain: up to this many chunks per lane the kernel is built for two waves per SIMD (256 registers each).
-// Not the kernel of a runtime-compiled density: its workgroup's LDS (four chains' scratch + the model's shared block) leaves one
-// workgroup per CU anyway, and the density wants the registers — radon, 512 / 2048 chains, same box: 56.6 -> 62.1 / 96.2 -> 107.7 M
-// leapfrogs/s for the traced torch density, 50.3 -> 51.5 / 90.6 -> 93.7 for the one written as expressions (profiles/r5_jit_occupancy.txt);
-// a small density stays below 256 registers by itself.
-#ifndef NPHIP_W1_OCC2_MAX
-#if NPHIP_JIT
-#define NPHIP_W1_OCC2_MAX 0
-#else
-#define NPHIP_W1_OCC2_MAX 3
-#endif
-#endif
-// register kernels with several waves per chain: up to this many chunks per wave run two waves per SIMD (256 registers each)
-#ifndef NPHIP_RW_OCC2_MAX
-#define NPHIP_RW_OCC2_MAX 4
-#endif
-#ifndef NPHIP_CB_OCC
-// waves per SIMD the launch-per-evaluation (callback) kernels are compiled for.  Two: 256 registers per lane, (almost) nothing
-// spilled.  Measured at four waves per SIMD (128 registers, every chain of a 1024-chain batch x 4 waves on the device at once):
-// 82 spilled VGPRs, eleven of them stored by every wave of every launch — 23 MB of scratch traffic per launch in a kernel that
-// is bound by its memory traffic — 38.4 us per launch against 33.5 (profiles/r4_callback_kernels.txt)
-#define NPHIP_CB_OCC(W) 2
-#endif
-#ifndef NPHIP_LEAN_OCC
-// waves per SIMD of the lean kernels: 8 waves = one chain per CU at 256 VGPRs per wave (4 waves: 512 = VGPRs + AGPRs)
-#define NPHIP_LEAN_OCC(W) ((W) <= 4 ? 1 : ((W) <= 8 ? 2 : 4))
-#endif
 
 __device__ __forceinline__ void chain_sync() {
     // make this chain's global stores visible to all of its lanes/waves
@@ -545,10 +519,11 @@ struct Machine {
     // launch-per-evaluation kernels: the end of a draw is cut into slices of a launch each (engine_types.h: PH_DRAW_END / PH_DRAW_BEGIN)
     static constexpr bool SLICED = !INK && NV == 0;
     static constexpr bool DENS = REMOTE && (NPHIP_JIT != 0);   // ... by calling the model's own device function (runtime-compiled density)
-    // NORING (developer builds only, -DNPHIP_DEV_W1NV=9..12): one wave per chain with more than 8 chunks per lane — the leaf of the 8-chunk kernels without
-    // their LDS ring (four rings of that width do not fit a CU's LDS): every (p, rho) summary goes to its P-slot, the level-1 merges read them back from L2.
-    // Measured in round 6 against the shipped two waves per chain (profiles/r6_step_at_d1025_one_wave_no_ring_rejected.txt): D = 1100 114.5 against 123.2 M
-    // leapfrogs/s, D = 1280 68 against 124 (the 10-chunk leaf spills), D = 1536 44 against 110 — the ring is worth more than the second wave costs.  Not shipped.
+    // NORING: one wave per chain with more than 8 chunks per lane — the leaf of the 8-chunk kernels without their LDS ring (four rings of that width do
+    // not fit a CU's LDS): every (p, rho) summary goes to its P-slot, the level-1 merges read them back from L2.  What a runtime-compiled density of more
+    // than 1024 dimensions runs when it is compiled for one wave per chain.  No fused family has it (kernel_families.h): measured in round 6 against the
+    // shipped two waves per chain (profiles/r6_step_at_d1025_one_wave_no_ring_rejected.txt), D = 1100 114.5 against 123.2 M leapfrogs/s, D = 1280 68
+    // against 124 (the 10-chunk leaf spills), D = 1536 44 against 110 — the ring is worth more than the second wave costs.
     static constexpr bool NORING = !LEAN && !LR && W == 1 && NV > 8;
     static constexpr bool DG = REMOTE && (NPHIP_JIT == 0) && TAG == 2;   // ... by the launch-wide GEMM of the dense-precision Gaussian (dg_round)
     LdsDouble dens_lds = nullptr;   // DENS: this wave's LDS scratch for the density
@@ -1557,7 +1532,7 @@ struct Machine {
 #ifndef NPHIP_CB_CHUNKS
 #define NPHIP_CB_CHUNKS 2
 #endif
-    static constexpr int CBK = NPHIP_CB_CHUNKS;   // chunks per wave the fused leaf holds in registers (host.hip: choose_waves_callback)
+    static constexpr int CBK = NPHIP_CB_CHUNKS;   // chunks per wave the fused leaf holds in registers (host.hip: choose_geometry)
     static constexpr int kParkMax = 3 + 6 * (kMaxDepthCap - 1) + 6;   // K, level 0, six values per level >= 1 and for the top-level merge
     struct CbCrit {
         uint32_t bits;        // bit k: the criteria of merge level k say "turning"  (level 0 = the pair (source, new leaf))
@@ -2694,7 +2669,7 @@ struct Machine {
     // whole summary fits (3 x 48 KB); above, the first KP chunks of p and KR chunks of rho of every wave do (D = 10 000: 18 of
     // the 20 chunks of p) and the rest goes through its P-slot as before.  Every wave touches only its own chunks: no barrier.
     // The LDS part is written back at a launch boundary (flush).
-    static constexpr int LR_FREE = (LEAN && W == 4) ? (163840 - (NVX > 20 ? 12288 : 8192) - NVX * W * (NPHIP_CHUNK * 8)) / (W * (NPHIP_CHUNK * 8)) : 0;   // chunks per wave (the kernel's static LDS grows with the edge buffer: 8.1 KB at 20 chunks)
+    static constexpr int LR_FREE = LEAN ? lean_free_chunks(W, NVX) : 0;   // chunks per wave (kernel_families.h)
     static constexpr int KP = LR_FREE < 0 ? 0 : (LR_FREE < NVX ? LR_FREE : NVX);
     static constexpr int KR = (LR_FREE - KP) < 0 ? 0 : ((LR_FREE - KP) < NVX ? (LR_FREE - KP) : NVX);
     static constexpr bool LRING = KP > 0;
@@ -4008,7 +3983,8 @@ struct Machine {
 // against 389: profiles/r5_small_kernels_register_cap.txt)
 // DENSEG: the resident form of the dense-precision Gaussian (REMOTE with the launch-wide GEMM as the evaluation: Machine<..., DG>, dg_round)
 template <bool FUSED, int W, int NV, bool LEAN = false, bool REMOTE = false, bool LR = false, bool WIDE = false, bool DENSEG = false>
-__global__ __launch_bounds__(W == 1 ? 256 : 64 * W) __attribute__((amdgpu_waves_per_eu(LEAN ? NPHIP_LEAN_OCC(W) : ((NV > 0 && !LR && !WIDE && NV <= (W == 1 ? NPHIP_W1_OCC2_MAX : NPHIP_RW_OCC2_MAX)) ? 2 : ((!FUSED && NV == 0 && !REMOTE) ? NPHIP_CB_OCC(W) : 1)), LEAN ? NPHIP_LEAN_OCC(W) : ((NV > 0 && !LR && !WIDE && NV <= (W == 1 ? NPHIP_W1_OCC2_MAX : NPHIP_RW_OCC2_MAX)) ? 2 : 8)))) void k_advance(const Args* __restrict__ Ap, int max_evals, int have_result, const LaunchSlice sl) {
+__global__ __launch_bounds__(W == 1 ? 256 : 64 * W) __attribute__((amdgpu_waves_per_eu(min_waves<FUSED, W, NV, LEAN, REMOTE, LR, WIDE>(), max_waves<FUSED, W, NV, LEAN, REMOTE, LR, WIDE>())))
+void k_advance(const Args* __restrict__ Ap, int max_evals, int have_result, const LaunchSlice sl) {
     const NPHIP_CONST Args& A = *(const NPHIP_CONST Args*)Ap;
     constexpr int WAVES = (W == 1) ? 4 : W;
     __shared__ Ctl s_ctl[WAVES];
@@ -4153,16 +4129,14 @@ __global__ __launch_bounds__(W == 1 ? 256 : 64 * W) __attribute__((amdgpu_waves_
 }
 
 // ----------------------------------------------------------------------------------------
-// launch tables.  The file is compiled as twelve translation units in parallel (Makefile: -DNPHIP_PART=0..6, 8..12), each instantiating
-// one family of kernels; without NPHIP_PART (developer builds, see the NPHIP_DEV_* macros) everything is in one.
+// launchers.  The file is compiled as twelve translation units in parallel (Makefile: -DNPHIP_PART=0..6, 8..12), each instantiating the
+// kernel families that kernel_families.h assigns to it; without NPHIP_PART (developer builds: -DNPHIP_ONLY_FAMILY=, same header)
+// everything is in one.
 // ----------------------------------------------------------------------------------------
 #ifndef NPHIP_PART
 #define NPHIP_PART -1
 #endif
 #define NPHIP_HAS(p) (NPHIP_PART == -1 || NPHIP_PART == (p))
-#if defined(NPHIP_DEV_LEAN) || defined(NPHIP_DEV_W1NV) || defined(NPHIP_DEV_CB_W) || defined(NPHIP_DEV_W1NV_LR) || defined(NPHIP_DEV_RW_LR_W) || defined(NPHIP_DEV_DG_NV)
-#define NPHIP_DEV_BUILD 1   // one kernel instantiation only: seconds instead of minutes
-#endif
 
 hipError_t launch_fam_w1(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl);              // part 0
 hipError_t launch_fam_w1_lr(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl);           // part 8
@@ -4172,125 +4146,42 @@ hipError_t launch_fam_rw(const Args& a, const Args* d_args, int W, hipStream_t s
 hipError_t launch_fam_rw_lr(const Args& a, const Args* d_args, int W, hipStream_t st, const LaunchSlice sl);    // part 9
 hipError_t launch_fam_mem(const Args& a, const Args* d_args, bool fused, int W, hipStream_t st, const LaunchSlice sl);   // part 4
 
-// dynamic LDS of the lean kernels: sigma^2, and (4 waves per chain) as much of one (p, rho) summary as fits beside it (Machine::LR_FREE)
-static size_t lean_dyn_lds(const Args& a, int W) {
-    size_t dyn = (size_t)a.ld * 8;
-    if (W == 4) {
-        const long chunk_bytes = 4 * 1024, free_chunks = (163840 - (a.reg_nv > 20 ? 12288 : 8192) - (long)a.reg_nv * chunk_bytes) / chunk_bytes;   // (= Machine::LR_FREE)
-        dyn += (size_t)std::max(0l, std::min(free_chunks, 2l * a.reg_nv)) * chunk_bytes;
-    }
-    return dyn;
+// One launch of family F's kernel with W waves per chain and nv chunks per wave: grid and block from the table, the instantiation by
+// dispatch over the family's waves and chunk range; hipErrorInvalidValue where the family (or a developer build) has no such kernel.
+template <const KernelFamily& F, bool FUSED = F.fused>
+static hipError_t launch_family(int W, int nv, size_t dyn, const Args* d_args, int max_evals, int have_result, hipStream_t st, const LaunchSlice& sl) {
+    static_assert(NPHIP_HAS(F.part), "a family is instantiated in its own translation unit");
+    bool launched = false;
+    dispatch_value<16, 8, 4, 2, 1>(W, [&](auto w) {
+        constexpr int WW = decltype(w)::value;
+        if constexpr ((F.waves & WW) != 0) dispatch_range<F.nv_lo, F.nv_hi>(nv, [&](auto n) {
+            constexpr int NN = decltype(n)::value;
+            if constexpr (built(F, WW, NN)) {
+                const unsigned groups = ((unsigned)sl.chain_n + chains_per_group(WW) - 1) / chains_per_group(WW);
+                hipLaunchKernelGGL((k_advance<FUSED, WW, NN, F.lean, F.remote, F.lr, F.wide, F.denseg>), dim3(groups), dim3(group_threads(WW)), dyn, st, d_args,
+                                   max_evals, have_result, sl);
+                launched = true;
+            }
+        });
+    });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
-#define NPHIP_LAUNCH_LEAN(WW, NN) hipLaunchKernelGGL((k_advance<true, WW, NN, true>), g, b, dyn, st, d_args, a.max_evals, a.have_result, sl)
+// ... of a fused model: chunks, launch length and dynamic LDS from the engine's argument block
+template <const KernelFamily& F, bool FUSED = F.fused>
+static hipError_t launch_family(const Args& a, int W, int nv, const Args* d_args, hipStream_t st, const LaunchSlice& sl) {
+    return launch_family<F, FUSED>(W, nv, dyn_lds_bytes(F, W, nv, a.ld, a.sig_lds != 0), d_args, a.max_evals, a.have_result, st, sl);
+}
 
 #if NPHIP_HAS(1)
-// lean register-resident kernels, 4 waves per chain (4096 < D <= 12288): state spread over VGPRs + AGPRs (one wave per SIMD), 9..24
-// chunks per wave; one workgroup = one chain
-hipError_t launch_fam_lean4(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl) {
-    const dim3 g((unsigned)sl.chain_n), b(256);
-    const size_t dyn = lean_dyn_lds(a, 4);
-    (void)g; (void)b; (void)dyn;
-    switch (a.reg_nv) {
-#if defined(NPHIP_DEV_LEAN) && defined(NPHIP_DEV_W) && defined(NPHIP_DEV_NC)
-#if NPHIP_DEV_W == 4
-        case NPHIP_DEV_NC: NPHIP_LAUNCH_LEAN(4, NPHIP_DEV_NC); break;
-#endif
-#elif !defined(NPHIP_DEV_BUILD)
-        case 9: NPHIP_LAUNCH_LEAN(4, 9); break;
-        case 10: NPHIP_LAUNCH_LEAN(4, 10); break;
-        case 11: NPHIP_LAUNCH_LEAN(4, 11); break;
-        case 12: NPHIP_LAUNCH_LEAN(4, 12); break;
-        case 13: NPHIP_LAUNCH_LEAN(4, 13); break;
-        case 14: NPHIP_LAUNCH_LEAN(4, 14); break;
-        case 15: NPHIP_LAUNCH_LEAN(4, 15); break;
-        case 16: NPHIP_LAUNCH_LEAN(4, 16); break;
-        case 17: NPHIP_LAUNCH_LEAN(4, 17); break;
-        case 18: NPHIP_LAUNCH_LEAN(4, 18); break;
-        case 19: NPHIP_LAUNCH_LEAN(4, 19); break;
-        case 20: NPHIP_LAUNCH_LEAN(4, 20); break;
-        // 21 .. 24 chunks per wave (10 240 < D <= 12 288, round 6): the state no longer fits the 512 registers of a lane — 16 per chunk beside
-        // a working set of ~130 — and the build spills (22 chunks: 216 bytes of scratch per lane, 24: 456); still 1.6 x / 1.3 x the
-        // memory-resident kernels that ran these rows before (D = 11 264: 8.6 against 5.4 M leapfrogs/s, D = 12 000: 6.5 against 5.0;
-        // profiles/r6_lean4_beyond_20_chunks.txt)
-        case 21: NPHIP_LAUNCH_LEAN(4, 21); break;
-        case 22: NPHIP_LAUNCH_LEAN(4, 22); break;
-        case 23: NPHIP_LAUNCH_LEAN(4, 23); break;
-        case 24: NPHIP_LAUNCH_LEAN(4, 24); break;
-#endif
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
+hipError_t launch_fam_lean4(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl) { return launch_family<kLean4>(a, 4, a.reg_nv, d_args, st, sl); }
 #endif
 
 #if NPHIP_HAS(2)
-// lean register-resident kernels, 8 waves per chain (on request: waves_per_chain = 8), 1..10 chunks per wave
-hipError_t launch_fam_lean8(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl) {
-    const dim3 g((unsigned)sl.chain_n), b(512);
-    const size_t dyn = lean_dyn_lds(a, 8);
-    (void)g; (void)b; (void)dyn;
-    switch (a.reg_nv) {
-#if defined(NPHIP_DEV_LEAN) && defined(NPHIP_DEV_NC)
-#if !defined(NPHIP_DEV_W) || NPHIP_DEV_W == 8
-        case NPHIP_DEV_NC: NPHIP_LAUNCH_LEAN(8, NPHIP_DEV_NC); break;
+hipError_t launch_fam_lean8(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl) { return launch_family<kLean8>(a, 8, a.reg_nv, d_args, st, sl); }
 #endif
-#elif !defined(NPHIP_DEV_BUILD)
-        case 1: NPHIP_LAUNCH_LEAN(8, 1); break;
-        case 2: NPHIP_LAUNCH_LEAN(8, 2); break;
-        case 3: NPHIP_LAUNCH_LEAN(8, 3); break;
-        case 4: NPHIP_LAUNCH_LEAN(8, 4); break;
-        case 5: NPHIP_LAUNCH_LEAN(8, 5); break;
-        case 6: NPHIP_LAUNCH_LEAN(8, 6); break;
-        case 7: NPHIP_LAUNCH_LEAN(8, 7); break;
-        case 8: NPHIP_LAUNCH_LEAN(8, 8); break;
-        case 9: NPHIP_LAUNCH_LEAN(8, 9); break;
-        case 10: NPHIP_LAUNCH_LEAN(8, 10); break;
-#endif
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-#endif
-#undef NPHIP_LAUNCH_LEAN
 
 #if NPHIP_HAS(3)
-// register-resident, several waves per chain (1024 < D <= 4096, or fewer chains than SIMDs): one workgroup = one chain
-hipError_t launch_fam_rw(const Args& a, const Args* d_args, int W, hipStream_t st, const LaunchSlice sl) {
-#define NPHIP_LAUNCH_RW(WW, NN) hipLaunchKernelGGL((k_advance<true, WW, NN>), g, b, 0, st, d_args, a.max_evals, a.have_result, sl)
-#if defined(NPHIP_DEV_RW_W) && defined(NPHIP_DEV_RW_NV)
-    const dim3 g((unsigned)sl.chain_n), b(64 * W);
-    if (W != NPHIP_DEV_RW_W || a.reg_nv != NPHIP_DEV_RW_NV) return hipErrorInvalidValue;
-    NPHIP_LAUNCH_RW(NPHIP_DEV_RW_W, NPHIP_DEV_RW_NV);
-    return hipGetLastError();
-#elif defined(NPHIP_DEV_BUILD)
-    return hipErrorInvalidValue;
-#else
-    const dim3 g((unsigned)sl.chain_n), b(64 * W);
-    if (W == 2) switch (a.reg_nv) {
-        case 1: NPHIP_LAUNCH_RW(2, 1); break;
-        case 2: NPHIP_LAUNCH_RW(2, 2); break;
-        case 3: NPHIP_LAUNCH_RW(2, 3); break;
-        case 4: NPHIP_LAUNCH_RW(2, 4); break;
-        case 5: NPHIP_LAUNCH_RW(2, 5); break;
-        case 6: NPHIP_LAUNCH_RW(2, 6); break;
-        case 7: NPHIP_LAUNCH_RW(2, 7); break;
-        case 8: NPHIP_LAUNCH_RW(2, 8); break;
-        default: return hipErrorInvalidValue;
-    } else switch (a.reg_nv) {
-        case 1: NPHIP_LAUNCH_RW(4, 1); break;
-        case 2: NPHIP_LAUNCH_RW(4, 2); break;
-        case 3: NPHIP_LAUNCH_RW(4, 3); break;
-        case 4: NPHIP_LAUNCH_RW(4, 4); break;
-        case 5: NPHIP_LAUNCH_RW(4, 5); break;
-        case 6: NPHIP_LAUNCH_RW(4, 6); break;
-        case 7: NPHIP_LAUNCH_RW(4, 7); break;
-        case 8: NPHIP_LAUNCH_RW(4, 8); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-#endif
-#undef NPHIP_LAUNCH_RW
-}
+hipError_t launch_fam_rw(const Args& a, const Args* d_args, int W, hipStream_t st, const LaunchSlice sl) { return launch_family<kRing>(a, W, a.reg_nv, d_args, st, sl); }
 #endif
 
 // The one-wave kernels with 2 .. 8 chunks per lane (128 < D <= 1024: the ENDOUT family, the headline's among them) are a translation unit of their
@@ -4302,150 +4193,34 @@ hipError_t launch_fam_rw(const Args& a, const Args* d_args, int W, hipStream_t s
 // +2.4 % / +5 %).  NOT the lean kernels (D = 10 000: 15.4 -> 12.6) and not the low-rank leaf (D = 1000, k = 16: 16.1 -> 14.7).
 // (profiles/r6_call_placement_and_draw_end.txt D)
 hipError_t launch_w1_noipra(int nv, const Args* d_args, hipStream_t st, const LaunchSlice sl, int me, int hr);
-#if NPHIP_HAS(12) && !defined(NPHIP_DEV_BUILD)
+#if NPHIP_HAS(12)
 hipError_t launch_w1_noipra(int nv, const Args* d_args, hipStream_t st, const LaunchSlice sl, int me, int hr) {
-    const dim3 g(((unsigned)sl.chain_n + 3) / 4), b(256);
-    switch (nv) {
-        // (2, 3 chunks per lane: built for two waves per SIMD — unless the job has no second wave to bring: k_advance<..., WIDE>)
-        case 2: if (sl.chain_n <= 1024) hipLaunchKernelGGL((k_advance<true, 1, 2, false, false, false, true>), g, b, 0, st, d_args, me, hr, sl);
-                else hipLaunchKernelGGL((k_advance<true, 1, 2>), g, b, 0, st, d_args, me, hr, sl);
-                break;
-        case 3: if (sl.chain_n <= 1024) hipLaunchKernelGGL((k_advance<true, 1, 3, false, false, false, true>), g, b, 0, st, d_args, me, hr, sl);
-                else hipLaunchKernelGGL((k_advance<true, 1, 3>), g, b, 0, st, d_args, me, hr, sl);
-                break;
-        case 4: hipLaunchKernelGGL((k_advance<true, 1, 4>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 5: hipLaunchKernelGGL((k_advance<true, 1, 5>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 6: hipLaunchKernelGGL((k_advance<true, 1, 6>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 7: hipLaunchKernelGGL((k_advance<true, 1, 7>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 8: hipLaunchKernelGGL((k_advance<true, 1, 8>), g, b, 0, st, d_args, me, hr, sl); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    // (2, 3 chunks per lane: built for two waves per SIMD — unless the job has no second wave to bring: k_advance<..., WIDE>)
+    if (sl.chain_n <= kWideMaxChains && has(kW1Wide, 1, nv)) return launch_family<kW1Wide>(1, nv, 0, d_args, me, hr, st, sl);
+    return launch_family<kW1>(1, nv, 0, d_args, me, hr, st, sl);
 }
 #endif
 
 #if NPHIP_HAS(0)
-// register-resident, one wave per chain (D <= 1024): four chains per workgroup, one instantiation per exact chunk count
 hipError_t launch_fam_w1(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl) {
-    const dim3 g(((unsigned)sl.chain_n + 3) / 4), b(256);
-    const int me = a.max_evals, hr = a.have_result;
-    (void)g; (void)b; (void)me; (void)hr;
-    switch (a.reg_nv) {
-#if defined(NPHIP_DEV_W1NV)
-        case NPHIP_DEV_W1NV: hipLaunchKernelGGL((k_advance<true, 1, NPHIP_DEV_W1NV>), g, b, 0, st, d_args, me, hr, sl); break;
-#elif !defined(NPHIP_DEV_BUILD)
-        case 1: hipLaunchKernelGGL((k_advance<true, 1, 1>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 2: case 3: case 4: case 5: case 6: case 7: case 8: return launch_w1_noipra((int)a.reg_nv, d_args, st, sl, me, hr);   // (part 12)
-#endif
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (has(kW1One, 1, a.reg_nv)) return launch_family<kW1One>(a, 1, a.reg_nv, d_args, st, sl);
+    return launch_w1_noipra((int)a.reg_nv, d_args, st, sl, a.max_evals, a.have_result);   // (part 12)
 }
 #endif
-
 
 #if NPHIP_HAS(8)
-// register-resident, one wave per chain, under the low-rank metric (settings.low_rank_metric; Machine<..., LR>): D <= 1024
-hipError_t launch_fam_w1_lr(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl) {
-    const dim3 g(((unsigned)sl.chain_n + 3) / 4), b(256);
-    const int me = a.max_evals, hr = a.have_result;
-    (void)g; (void)b; (void)me; (void)hr;
-    switch (a.reg_nv) {
-#if defined(NPHIP_DEV_W1NV_LR)
-        case NPHIP_DEV_W1NV_LR: hipLaunchKernelGGL((k_advance<true, 1, NPHIP_DEV_W1NV_LR, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-#elif !defined(NPHIP_DEV_BUILD)
-        case 1: hipLaunchKernelGGL((k_advance<true, 1, 1, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 2: hipLaunchKernelGGL((k_advance<true, 1, 2, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 3: hipLaunchKernelGGL((k_advance<true, 1, 3, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 4: hipLaunchKernelGGL((k_advance<true, 1, 4, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 5: hipLaunchKernelGGL((k_advance<true, 1, 5, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 6: hipLaunchKernelGGL((k_advance<true, 1, 6, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 7: hipLaunchKernelGGL((k_advance<true, 1, 7, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-        case 8: hipLaunchKernelGGL((k_advance<true, 1, 8, false, false, true>), g, b, 0, st, d_args, me, hr, sl); break;
-#endif
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
+hipError_t launch_fam_w1_lr(const Args& a, const Args* d_args, hipStream_t st, const LaunchSlice sl) { return launch_family<kW1Lr>(a, 1, a.reg_nv, d_args, st, sl); }
 #endif
 
 #if NPHIP_HAS(9)
-// register-resident, two / four waves per chain, under the low-rank metric: the geometries choose_waves() picks (1024 < D <= 2048:
-// two waves, 2048 < D <= 4096: four; 5..8 chunks per wave)
-hipError_t launch_fam_rw_lr(const Args& a, const Args* d_args, int W, hipStream_t st, const LaunchSlice sl) {
-#define NPHIP_LAUNCH_RW_LR(WW, NN) hipLaunchKernelGGL((k_advance<true, WW, NN, false, false, true>), g, b, 0, st, d_args, a.max_evals, a.have_result, sl)
-    const dim3 g((unsigned)sl.chain_n), b(64 * W);
-    (void)g; (void)b;
-#if defined(NPHIP_DEV_RW_LR_W) && defined(NPHIP_DEV_RW_LR_NV)
-    if (W != NPHIP_DEV_RW_LR_W || a.reg_nv != NPHIP_DEV_RW_LR_NV) return hipErrorInvalidValue;
-    NPHIP_LAUNCH_RW_LR(NPHIP_DEV_RW_LR_W, NPHIP_DEV_RW_LR_NV);
-    return hipGetLastError();
-#elif defined(NPHIP_DEV_BUILD)
-    return hipErrorInvalidValue;
-#else
-    if (W == 2) switch (a.reg_nv) {
-        case 5: NPHIP_LAUNCH_RW_LR(2, 5); break;
-        case 6: NPHIP_LAUNCH_RW_LR(2, 6); break;
-        case 7: NPHIP_LAUNCH_RW_LR(2, 7); break;
-        case 8: NPHIP_LAUNCH_RW_LR(2, 8); break;
-        default: return hipErrorInvalidValue;
-    } else switch (a.reg_nv) {
-        case 5: NPHIP_LAUNCH_RW_LR(4, 5); break;
-        case 6: NPHIP_LAUNCH_RW_LR(4, 6); break;
-        case 7: NPHIP_LAUNCH_RW_LR(4, 7); break;
-        case 8: NPHIP_LAUNCH_RW_LR(4, 8); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-#endif
-#undef NPHIP_LAUNCH_RW_LR
-}
+hipError_t launch_fam_rw_lr(const Args& a, const Args* d_args, int W, hipStream_t st, const LaunchSlice sl) { return launch_family<kRingLr>(a, W, a.reg_nv, d_args, st, sl); }
 #endif
 
 #if NPHIP_HAS(4)
-// memory-resident kernels: fused models of any D and W (D > 10 240, store_divergences, no_register_kernel) and the two-phase
-// callback kernels
 template <bool FUSED>
 static hipError_t launch_mem_t(const Args& a, const Args* d_args, int W, hipStream_t st, const LaunchSlice sl) {
-#if defined(NPHIP_DEV_CB_W)   // developer build: the callback kernel of ONE geometry
-    if constexpr (!FUSED) {
-        if (W == NPHIP_DEV_CB_W && !a.lr_on) {
-            const unsigned n_ = (unsigned)sl.chain_n;
-            hipLaunchKernelGGL((k_advance<false, NPHIP_DEV_CB_W, 0>), dim3(NPHIP_DEV_CB_W == 1 ? (n_ + 3) / 4 : n_), dim3(NPHIP_DEV_CB_W == 1 ? 256 : 64 * NPHIP_DEV_CB_W),
-                               (NPHIP_DEV_CB_W >= 8 && a.sig_lds) ? (size_t)a.ld * 8 : 0, st, d_args, a.max_evals, a.have_result, sl);
-            return hipGetLastError();
-        }
-    }
-    return hipErrorInvalidValue;
-#elif defined(NPHIP_DEV_BUILD)
-    return hipErrorInvalidValue;
-#else
-    const unsigned n = (unsigned)sl.chain_n;
-    const int me = a.max_evals, hr = a.have_result;
-    if (FUSED && a.stream_cache && W == 1) {
-        // memory-resident kernel with the cursor's (sigma^2, grad, p, rho) cached in VGPRs between leaves.  Measured
-        // with more waves per chain (D > 1024) the cache costs occupancy or spills and does not pay; W == 1 only.
-        hipLaunchKernelGGL((k_advance<true, 1, -8>), dim3((n + 3) / 4), dim3(256), 0, st, d_args, me, hr, sl);
-        return hipGetLastError();
-    }
-    if (a.lr_on) switch (W) {   // the low-rank metric: the NV = -1 instantiations
-        case 1: hipLaunchKernelGGL((k_advance<FUSED, 1, -1>), dim3((n + 3) / 4), dim3(256), 0, st, d_args, me, hr, sl); return hipGetLastError();
-        case 2: hipLaunchKernelGGL((k_advance<FUSED, 2, -1>), dim3(n), dim3(128), 0, st, d_args, me, hr, sl); return hipGetLastError();
-        case 4: hipLaunchKernelGGL((k_advance<FUSED, 4, -1>), dim3(n), dim3(256), 0, st, d_args, me, hr, sl); return hipGetLastError();
-        case 8: hipLaunchKernelGGL((k_advance<FUSED, 8, -1>), dim3(n), dim3(512), a.sig_lds ? (size_t)a.ld * 8 : 0, st, d_args, me, hr, sl); return hipGetLastError();
-        case 16: hipLaunchKernelGGL((k_advance<FUSED, 16, -1>), dim3(n), dim3(1024), a.sig_lds ? (size_t)a.ld * 8 : 0, st, d_args, me, hr, sl); return hipGetLastError();
-        default: return hipErrorInvalidValue;
-    }
-    switch (W) {
-        case 1: hipLaunchKernelGGL((k_advance<FUSED, 1, 0>), dim3((n + 3) / 4), dim3(256), 0, st, d_args, me, hr, sl); break;
-        case 2: hipLaunchKernelGGL((k_advance<FUSED, 2, 0>), dim3(n), dim3(128), 0, st, d_args, me, hr, sl); break;
-        case 4: hipLaunchKernelGGL((k_advance<FUSED, 4, 0>), dim3(n), dim3(256), 0, st, d_args, me, hr, sl); break;
-        case 8: hipLaunchKernelGGL((k_advance<FUSED, 8, 0>), dim3(n), dim3(512), a.sig_lds ? (size_t)a.ld * 8 : 0, st, d_args, me, hr, sl); break;
-        case 16: hipLaunchKernelGGL((k_advance<FUSED, 16, 0>), dim3(n), dim3(1024), a.sig_lds ? (size_t)a.ld * 8 : 0, st, d_args, me, hr, sl); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-#endif
+    if (FUSED && a.stream_cache && W == 1) return launch_family<kMemoryCached>(a, 1, kMemoryCached.nv_lo, d_args, st, sl);
+    return launch_family<kMemory, FUSED>(a, W, a.lr_on ? -1 : 0, d_args, st, sl);   // (the low-rank metric: the NV = -1 instantiations)
 }
 hipError_t launch_fam_mem(const Args& a, const Args* d_args, bool fused, int W, hipStream_t st, const LaunchSlice sl) {
     return fused ? launch_mem_t<true>(a, d_args, W, st, sl) : launch_mem_t<false>(a, d_args, W, st, sl);
@@ -4553,97 +4328,26 @@ hipError_t launch_advance(const Args& a, const Args* d_args, bool fused, int W, 
 #endif   // part 0
 
 #if NPHIP_HAS(5)
-
 // Resident launch of a host-callback job (k_advance<..., REMOTE>): `W` waves per chain with `nv` chunks of 128 elements each in
 // registers (dim <= 128 W nv; W = 1: four chains per workgroup, W = 2 / 4: one).  The slice names the groups and their
 // sequence numbers.
 hipError_t launch_remote_w1(const Args* d_args, int nv, hipStream_t st, const LaunchSlice& sl);     // part 5
 hipError_t launch_remote_wn(const Args* d_args, int W, int nv, hipStream_t st, const LaunchSlice& sl);   // part 6
-#define NPHIP_LAUNCH_REMOTE(WW, NN) hipLaunchKernelGGL((k_advance<false, WW, NN, false, true>), g, b, 0, st, d_args, 0, 0, sl)
-hipError_t launch_remote_w1(const Args* d_args, int nv, hipStream_t st, const LaunchSlice& sl) {
-#ifdef NPHIP_DEV_BUILD
-    return hipErrorInvalidValue;
-#else
-    const dim3 g(((unsigned)sl.chain_n + 3) / 4), b(256);
-    switch (nv) {
-        case 1: NPHIP_LAUNCH_REMOTE(1, 1); break;
-        case 2: NPHIP_LAUNCH_REMOTE(1, 2); break;
-        case 3: NPHIP_LAUNCH_REMOTE(1, 3); break;
-        case 4: NPHIP_LAUNCH_REMOTE(1, 4); break;
-        case 5: NPHIP_LAUNCH_REMOTE(1, 5); break;
-        case 6: NPHIP_LAUNCH_REMOTE(1, 6); break;
-        case 7: NPHIP_LAUNCH_REMOTE(1, 7); break;
-        case 8: NPHIP_LAUNCH_REMOTE(1, 8); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-#endif
-}
+hipError_t launch_remote_w1(const Args* d_args, int nv, hipStream_t st, const LaunchSlice& sl) { return launch_family<kRemoteW1>(1, nv, 0, d_args, 0, 0, st, sl); }
 hipError_t launch_remote(const Args* d_args, int W, int nv, hipStream_t st, const LaunchSlice& sl) {
     return W == 1 ? launch_remote_w1(d_args, nv, st, sl) : launch_remote_wn(d_args, W, nv, st, sl);
 }
-#undef NPHIP_LAUNCH_REMOTE
-
 #endif   // part 5
 
 #if NPHIP_HAS(6)
-#define NPHIP_LAUNCH_REMOTE(WW, NN) hipLaunchKernelGGL((k_advance<false, WW, NN, false, true>), g, b, 0, st, d_args, 0, 0, sl)
-hipError_t launch_remote_wn(const Args* d_args, int W, int nv, hipStream_t st, const LaunchSlice& sl) {
-#ifdef NPHIP_DEV_BUILD
-    return hipErrorInvalidValue;
-#else
-    const dim3 g((unsigned)sl.chain_n), b(64 * W);
-    if (W == 2) switch (nv) {
-        case 1: NPHIP_LAUNCH_REMOTE(2, 1); break;
-        case 2: NPHIP_LAUNCH_REMOTE(2, 2); break;
-        case 3: NPHIP_LAUNCH_REMOTE(2, 3); break;
-        case 4: NPHIP_LAUNCH_REMOTE(2, 4); break;
-        case 5: NPHIP_LAUNCH_REMOTE(2, 5); break;
-        case 6: NPHIP_LAUNCH_REMOTE(2, 6); break;
-        case 7: NPHIP_LAUNCH_REMOTE(2, 7); break;
-        case 8: NPHIP_LAUNCH_REMOTE(2, 8); break;
-        default: return hipErrorInvalidValue;
-    } else if (W == 4) switch (nv) {
-        case 1: NPHIP_LAUNCH_REMOTE(4, 1); break;
-        case 2: NPHIP_LAUNCH_REMOTE(4, 2); break;
-        case 3: NPHIP_LAUNCH_REMOTE(4, 3); break;
-        case 4: NPHIP_LAUNCH_REMOTE(4, 4); break;
-        case 5: NPHIP_LAUNCH_REMOTE(4, 5); break;
-        case 6: NPHIP_LAUNCH_REMOTE(4, 6); break;
-        case 7: NPHIP_LAUNCH_REMOTE(4, 7); break;
-        case 8: NPHIP_LAUNCH_REMOTE(4, 8); break;
-        default: return hipErrorInvalidValue;
-    } else return hipErrorInvalidValue;
-    return hipGetLastError();
-#endif
-}
-#undef NPHIP_LAUNCH_REMOTE
+hipError_t launch_remote_wn(const Args* d_args, int W, int nv, hipStream_t st, const LaunchSlice& sl) { return launch_family<kRemoteWn>(W, nv, 0, d_args, 0, 0, st, sl); }
 #endif   // part 6
-
 
 #if NPHIP_HAS(11)
 // Resident launch of the dense-precision Gaussian (k_advance<..., REMOTE, DENSEG>): one wave per chain, `nv` chunks of 128 dimensions,
 // every chain of the job on the device at once (<= 1024: one workgroup of four chains per CU) — the launch's roll call makes sure.
 hipError_t launch_dense_resident(const Args* d_args, int nv, int max_evals, hipStream_t st, const LaunchSlice sl) {
-    const dim3 g((unsigned)((sl.chain_n + 3) / 4)), b(256);
-#define NPHIP_LAUNCH_DG(NN) hipLaunchKernelGGL((k_advance<false, 1, NN, false, true, false, false, true>), g, b, 0, st, d_args, max_evals, 0, sl)
-    switch (nv) {
-#ifdef NPHIP_DEV_DG_NV
-        case NPHIP_DEV_DG_NV: NPHIP_LAUNCH_DG(NPHIP_DEV_DG_NV); break;
-#else
-        case 1: NPHIP_LAUNCH_DG(1); break;
-        case 2: NPHIP_LAUNCH_DG(2); break;
-        case 3: NPHIP_LAUNCH_DG(3); break;
-        case 4: NPHIP_LAUNCH_DG(4); break;
-        case 5: NPHIP_LAUNCH_DG(5); break;
-        case 6: NPHIP_LAUNCH_DG(6); break;
-        case 7: NPHIP_LAUNCH_DG(7); break;
-        case 8: NPHIP_LAUNCH_DG(8); break;
-#endif
-        default: return hipErrorInvalidValue;
-    }
-#undef NPHIP_LAUNCH_DG
-    return hipGetLastError();
+    return launch_family<kDenseResident>(1, nv, 0, d_args, max_evals, 0, st, sl);
 }
 #endif   // part 11
 

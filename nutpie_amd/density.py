@@ -190,7 +190,7 @@ def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verb
         raise ValueError("waves_per_chain must be 1, 2 or 4")
     nv = ((int(ndim) + 127) // 128 + waves - 1) // waves   # chunks of 128 dimensions per wave
     src = generated_source(user_source, layout)
-    deps = [os.path.join(_CSRC, f) for f in ("kernels.hip", "engine_types.h", "dense_tile.h")] + [os.path.join(_INCLUDE, "nphip_spec.h")]
+    deps = [os.path.join(_CSRC, f) for f in ("kernels.hip", "engine_types.h", "kernel_families.h", "dense_tile.h")] + [os.path.join(_INCLUDE, "nphip_spec.h")]
     if '#include "chain_linalg.h"' in user_source:
         deps.append(os.path.join(_CSRC, "chain_linalg.h"))
     if '#include "chain_scan.h"' in user_source:

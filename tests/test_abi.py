@@ -193,6 +193,18 @@ def test_build_configuration_of_the_families_measured_without_interprocedural_al
     generic = re.search(r"^kernels_p%\.o: kernels\.hip.*\n\t(.*)$", mk, re.M)
     assert generic and "enable-ipra" not in generic.group(1)
     src = open(os.path.join(root, "nutpie_amd", "csrc", "kernels.hip")).read()
-    assert "#if NPHIP_HAS(12) && !defined(NPHIP_DEV_BUILD)\nhipError_t launch_w1_noipra(" in src
+    # the one-wave kernels with 2 .. 8 chunks per lane are instantiated by launch_w1_noipra alone, which part 12 alone compiles, and the table
+    # of families says so (launch_family refuses at compile time to instantiate a family outside its part)
+    assert "#if NPHIP_HAS(12)\nhipError_t launch_w1_noipra(" in src and src.count("launch_family<kW1>(") == 1 and src.count("launch_family<kW1Wide>(") == 1
+    noipra = src[src.index("#if NPHIP_HAS(12)\nhipError_t launch_w1_noipra("):]
+    noipra = noipra[:noipra.index("#endif")]
+    assert "launch_family<kW1>(" in noipra and "launch_family<kW1Wide>(" in noipra
+    assert 'static_assert(NPHIP_HAS(F.part), "a family is instantiated in its own translation unit");' in src
+    fam = open(os.path.join(root, "nutpie_amd", "csrc", "kernel_families.h")).read()
+    rows = {m.group(1): [c.strip() for c in m.group(2).split(",")] for m in re.finditer(r"^inline constexpr KernelFamily (k\w+)\s*= \{(.*)\};$", fam, re.M)}
+    assert rows["kW1"][:8] == ["Family::w1", "true"] + ["false"] * 5 + ["1"] and rows["kW1"][8:11] == ["2", "8", "12"]      # W = 1, NV 2 .. 8, part 12
+    assert rows["kW1Wide"][5] == "true" and rows["kW1Wide"][7:11] == ["1", "2", "3", "12"]
+    assert rows["kDenseResident"][10] == "11"
+    assert sorted(k for k, r in rows.items() if r[10] in ("11", "12")) == ["kDenseResident", "kW1", "kW1Wide"]
     dens = open(os.path.join(root, "nutpie_amd", "density.py")).read()
     assert 'flags = (_FLAGS + ["-mllvm", "-enable-ipra=0", "-DNPHIP_JIT_DENSITY=1"' in dens

@@ -333,6 +333,48 @@ def test_evaluation_pool_runs_every_row_exactly_once(threads, use):
     assert 1 <= cores <= os.cpu_count()
 
 
+def test_geometry_choice_by_dimension_and_request():
+    """The job geometry — waves per chain, kernel family, chunks per wave, padded row length — is one pure function of the model and the
+    request (host.hip: choose_geometry) over the table of kernel families (csrc/kernel_families.h).  The rows are what the engine chose
+    before the table existed; and whatever it chooses, for every dimension up to 13 000 and every accepted number of waves, is an
+    instantiation the table has (a geometry without a kernel would otherwise only show on a GPU, as hipErrorInvalidValue)."""
+    from nutpie_amd import _lib
+
+    geo = _lib.test_choose_geometry
+
+    def row(g):
+        return (g["W"], g["family"], g["NV"], g["ld"])
+
+    fused = {1: (1, "w1", 1, 128), 128: (1, "w1", 1, 128), 129: (1, "w1", 2, 256), 1024: (1, "w1", 8, 1024), 1025: (2, "ring", 5, 1280),
+             2048: (2, "ring", 8, 2048), 2049: (4, "ring", 5, 2560), 4096: (4, "ring", 8, 4096), 4097: (4, "lean", 9, 4608),
+             10240: (4, "lean", 20, 10240), 10241: (4, "lean", 21, 10752), 12288: (4, "lean", 24, 12288), 12289: (8, "memory", 0, 12416)}
+    for dim, want in fused.items():
+        g = geo(dim)
+        assert row(g) == want, (dim, g)
+        assert g["lean"] == (want[1] == "lean") and g["sig_lds"] == (dim == 12289) and not g["stream_cache"] and not g["no_register_kernel"]
+    # requested waves per chain
+    assert row(geo(1000, waves_per_chain=4)) == (4, "ring", 2, 1024)
+    assert row(geo(5003, waves_per_chain=8))[:3] == (8, "lean", 5) and row(geo(10000, waves_per_chain=8))[:3] == (8, "lean", 10)
+    assert row(geo(10500, waves_per_chain=8))[:3] == (8, "memory", 0) and row(geo(9000, waves_per_chain=16))[:3] == (16, "memory", 0)
+    # the low-rank metric: the register leaf in the default geometries up to D = 4096, the memory-resident kernels elsewhere
+    assert row(geo(1000, low_rank_metric=True))[:3] == (1, "w1_lr", 8) and row(geo(1025, low_rank_metric=True))[:3] == (2, "ring_lr", 5)
+    for g, w in ((geo(1000, waves_per_chain=4, low_rank_metric=True), 4), (geo(5000, low_rank_metric=True), 4)):
+        assert row(g)[:3] == (w, "memory", -1) and g["no_register_kernel"]
+    # no_register_kernel: the memory-resident kernel, one wave per chain with the cursor cached in registers unless told otherwise
+    g = geo(700, no_register_kernel=True)
+    assert row(g) == (1, "memory", -8, 768) and g["stream_cache"]
+    g = geo(700, no_register_kernel=True, no_stream_cache=True)
+    assert row(g) == (1, "memory", 0, 768) and not g["stream_cache"]
+    # device callbacks: the fewest waves that keep a row within two chunks per wave
+    assert [geo(d, kind=2)["W"] for d in (256, 257, 1000, 4096, 5000)] == [1, 2, 4, 16, 16]
+    assert all(row(geo(d, kind=2))[1:3] == ("memory", 0) for d in (256, 5000))
+    # every choice has its kernel
+    for kw in (dict(), dict(low_rank_metric=True), dict(no_register_kernel=True), dict(kind=2)):
+        for w in (0, 1, 2, 4, 8, 16):
+            bad = [d for d in range(1, 13001) if not geo(d, waves_per_chain=w, **kw)["in_table"]]
+            assert not bad, (kw, w, bad[:5])
+
+
 def test_sampler_constructors_do_not_drop_arguments_silently():
     """The reference's PySampler.from_pymc / from_stan / from_pyfunc take a progress type, a callback and a storage back-end
     (wrapper.rs:1189-1250).  Here progress is driven one layer up and there is no storage back-end: passing either raises."""
