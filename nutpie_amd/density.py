@@ -197,6 +197,8 @@ def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verb
         deps.append(os.path.join(_CSRC, "chain_scan.h"))
     if '#include "chain_matvec.h"' in user_source:
         deps.append(os.path.join(_CSRC, "chain_matvec.h"))
+    if '#include "chain_hmm.h"' in user_source:
+        deps.append(os.path.join(_CSRC, "chain_hmm.h"))
     h = hashlib.sha256()
     h.update(src.encode())
     for d in deps:

@@ -33,6 +33,11 @@ recurrence, ``init`` a scalar or a value on ``rows``), ``cumsum(x, along=None)``
 path, a GARCH(1, 1) variance or an exponential-smoothing level — a stage between loops that one device routine runs on the chain's
 wave(s) (``csrc/chain_scan.h``), up to four waves per chain.
 
+Hidden Markov models: ``hmm_marginal_lpdf(log_emission, transition, initial, along=None)`` sums a discrete latent state out with the
+scaled forward algorithm (Stan's ``hmm_marginal``), ``hmm_state_prob`` reports the filtered or smoothed state probabilities, and
+``m.transition_matrix(name, K, concentration)`` declares a K x K matrix of simplex rows — a stage between loops that one device
+routine runs on the chain's wave(s) (``csrc/chain_hmm.h``), K <= 16, up to four waves per chain.
+
 Also: ``m.matrix("X", values, dim="obs", cols="coef")`` and ``X @ beta`` (a design matrix: with up to 63 columns lowered to a sum over
 its columns, the transposed product to one wave-wide sum per column; with more — or ``stage=True``, or a ``B`` with several right-hand
 sides on a ``product(coef, rhs)`` — a stage between loops that reads the matrix from L2, ``csrc/chain_matvec.h``, DESIGN.md §11.7,
@@ -71,7 +76,7 @@ __all__ = ["Model", "Expr", "Matrix", "exp", "log", "log1p", "sqrt", "softplus",
            "inverse_gamma_lpdf", "beta_lpdf", "laplace_lpdf", "logistic_lpdf", "weibull_lpdf", "uniform_lpdf",
            "bernoulli_logit_lpmf", "binomial_logit_lpmf", "negative_binomial_log_lpmf", "poisson_log_lpmf", "dirichlet_lpdf", "flat_lpdf",
            "cholesky", "solve_lower", "log_det_chol", "mvnormal_lpdf", "lkj_corr_cholesky_lpdf",
-           "linear_recurrence", "cumsum", "column", "pack_columns"]
+           "linear_recurrence", "cumsum", "column", "pack_columns", "hmm_marginal_lpdf", "hmm_state_prob"]
 
 _WAVE = 64
 _SEG_BATCH = os.environ.get("NUTPIE_AMD_SEG_MODE", "select") != "loop"   # (developer switch: "loop" = plain loops over a segment)
@@ -633,7 +638,14 @@ def pack_columns(columns, dim: Dim) -> Expr:
     return Expr("rowpack", tuple(columns), dim, None)
 
 
-_STAGES = _MATOPS + _SCANOPS + _MVOPS
+# HMM stages (csrc/chain_hmm.h): ``hmm_fwd`` (args logE, P, pi) is the scaled forward algorithm, ``hmm_bwd`` (args logE, P, the forward
+# result) the backward pass with the adjoints of P and pi — what the gradient emits.  A stage has ONE stored result, so each packs its
+# arrays on a dimension of its own: [alpha: R T K | c: R T | m: R T] resp. [beta: R T K | w: R T K | Pbar: K K | pibar: K]; ``hmm_part``
+# (payload: the offset) reads one of them as a value on the dimension it belongs to, ``hmm_ll`` the steps' log c_t + m_t — element-wise
+# reads of the stored array, like ``rhscol``.  payload = (R, T, K).
+_HMMOPS = ("hmm_fwd", "hmm_bwd")
+MAX_HMM_STATES = 16   # a lane keeps its column (row) of the transition matrix in registers, a group of up to 16 lanes owns a series
+_STAGES = _MATOPS + _SCANOPS + _MVOPS + _HMMOPS
 
 
 def _scan(a, b, init, R: int, T: int, rows: Dim | None = None) -> Expr:
@@ -704,6 +716,97 @@ def _scan_grads(n: Expr, lam: Expr) -> tuple[Expr | None, Expr | None]:
             first_terms = at_first(a * lam, 0.0)
             gi = first_terms.sum() if init.dim is None else _segsum(first_terms, to_r)
     return ga, gi
+
+# --------------------------------------------------------------------------- hidden Markov models
+def _hmm_model(d: Dim, what: str):
+    m = d._model() if d._model is not None else None
+    if m is None:
+        raise ValueError(f"{what}: log_emission lives on a dimension of no Model")
+    return m
+
+
+def _hmm_forward(logE, P, pi, R: int, T: int, K: int, steps: Dim, what: str = "hmm_marginal_lpdf") -> Expr:
+    """the forward stage for ``logE`` on ANY fixed-size dimension of R T K elements (row-major), ``steps`` a dimension of R T elements —
+    what a front end that keeps its tensors flat calls (the torch tracer); the public functions are this on a ``Model.product``"""
+    logE, P, pi = Expr.wrap(logE), Expr.wrap(P), Expr.wrap(pi)
+    d = logE.dim
+    if d is None or d.size is None or d.size != R * T * K or steps.size != R * T:
+        raise ValueError(f"{what}: log_emission is a value on a fixed-size dimension (R series of T steps of K states)")
+    if P.dim is None or P.dim.size != K * K:
+        raise ValueError(f"{what}: transition is a K x K value on a fixed-size dimension (K = {K}: the states of log_emission)")
+    if pi.dim is not None and pi.dim.size != K:
+        raise ValueError(f"{what}: initial is a scalar or a value on the {K} states of log_emission")
+    m = _hmm_model(d, what)
+    if pi.dim is None:
+        pi = _bcast(pi, m.dim(f"{d.name}__hmm_k", K))
+    packed = m.dim(f"{d.name}__hmm_f", R * T * K + 2 * R * T)
+    F = Expr("hmm_fwd", (logE, P, pi), packed, (int(R), int(T), int(K)))
+    packed._hmm_back = m.dim(f"{d.name}__hmm_b", 2 * R * T * K + K * K + K)      # (the backward stage's, should the gradient or a smoothed value need it)
+    return F
+
+
+def _hmm_backward(F: Expr) -> Expr:
+    logE, P, _ = F.args
+    return Expr("hmm_bwd", (logE, P, F), F.dim._hmm_back, F.payload)
+
+
+def _hmm_part(X: Expr, offset: int, dim: Dim) -> Expr:
+    return Expr("hmm_part", (X,), dim, int(offset))
+
+
+def _hmm_lpdf(F: Expr, steps: Dim) -> Expr:
+    """sum over the R T steps of log c_t + m_t: the IR's own reduction over ``steps``"""
+    return Expr("hmm_ll", (F,), steps, F.payload).sum()
+
+
+def _hmm_prob(F: Expr, smoothed: bool) -> Expr:
+    d = F.args[0].dim
+    alpha = _hmm_part(F, 0, d)
+    return alpha * _hmm_part(_hmm_backward(F), 0, d) if smoothed else alpha
+
+
+def _hmm_shape(log_emission, along, what: str):
+    logE = Expr.wrap(log_emission)
+    d = logE.dim
+    if d is None or d.size is None or d.factors is None:
+        raise ValueError(f"{what}: log_emission is a value on a Model.product(time, state) or product(product(series, time), state)")
+    steps, state = d.factors
+    if steps.size is None or state.size is None:
+        raise ValueError(f"{what}: log_emission is a value on a dimension of fixed size")
+    if along is None or (steps.factors is None and along == steps.name):
+        return logE, 1, steps.size, state.size, steps
+    if steps.factors is None:
+        raise ValueError(f"{what}: along={along!r} names no axis of dimension {steps.name!r}")
+    series, time = steps.factors
+    if along == series.name and along != time.name:
+        raise ValueError(f"{what}: {along!r} is the outer axis of {steps.name!r}; the time axis must be the inner (second) one")
+    if along != time.name:
+        raise ValueError(f"{what}: along={along!r} names no axis of dimension {steps.name!r}")
+    return logE, series.size, time.size, state.size, steps
+
+
+def hmm_marginal_lpdf(log_emission, transition, initial, along: str | None = None) -> Expr:
+    """The log-likelihood of a hidden Markov model with its discrete state summed out (Stan's ``hmm_marginal``): ``sum_r log(pi^T
+    diag(e_r0) P diag(e_r1) P ... diag(e_r,T-1) 1)`` with ``e = exp(log_emission)``, by the scaled forward algorithm.
+    ``log_emission``: the log density of observation t under state k, a value on ``Model.product(time, state)`` — one series — or on
+    ``product(product(series, time), state)`` with ``along`` naming the time axis: every series its own chain of states, the values
+    summed.  ``transition``: K x K on a fixed-size dimension (row-major; row i the weights of the next state given state i —
+    ``Model.transition_matrix``); ``initial``: a value on the K states, or one number for all.  The rows of ``transition`` and
+    ``initial`` need not sum to one: the value is the general product above, and so is the gradient with respect to every element.
+    K <= 16.  A ``log_emission`` of -inf is an impossible state; a step at which every state is impossible makes the density
+    non-finite (a divergence); a NaN makes what depends on it NaN (not guarded)."""
+    logE, R, T, K, steps = _hmm_shape(log_emission, along, "hmm_marginal_lpdf")
+    return _hmm_lpdf(_hmm_forward(logE, transition, initial, R, T, K, steps), steps)
+
+
+def hmm_state_prob(log_emission, transition, initial, along: str | None = None, smoothed: bool = True) -> Expr:
+    """The probability of every state at every step given the observations (Stan's ``hmm_hidden_state_prob``), a value on the
+    dimension of ``log_emission``: given all of the series' observations when ``smoothed`` (alpha_t beta_t of the forward-backward
+    algorithm — the gradient of :func:`hmm_marginal_lpdf` with respect to ``log_emission``), given those up to the step otherwise
+    (the filtered alpha_t).  Meant for ``Model.deterministic``: with the same arguments as the model's ``hmm_marginal_lpdf`` it reads
+    the arrays the density computes anyway.  It carries no gradient."""
+    logE, R, T, K, steps = _hmm_shape(log_emission, along, "hmm_state_prob")
+    return _hmm_prob(_hmm_forward(logE, transition, initial, R, T, K, steps, "hmm_state_prob"), bool(smoothed))
 
 
 def stack(scalars, dim: Dim) -> Expr:
@@ -1033,6 +1136,19 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
             acc(a, Expr("matvec_t", (_bcast(g, d),), a.dim, n.payload))   # B-bar = X^T E-bar
         elif n.op == "matvec_t":
             acc(a, Expr("matvec", (_bcast(g, d),), a.dim, n.payload))     # G-bar = X C-bar
+        elif n.op == "hmm_ll":
+            if g.dim is not None and g.op == "gather" and g.args[0].op == "bcast":
+                g = g.args[0].args[0]      # (per-series values summed by the caller, as the torch op returns them: one scalar for every step)
+            if g.dim is not None:
+                raise NotImplementedError("the steps of an HMM likelihood carry one weight: their sum is what is differentiated")
+            logE, P, pi = a.args
+            R, T, K = n.payload
+            back = _hmm_backward(a)
+            acc(logE, g * (_hmm_part(a, 0, logE.dim) * _hmm_part(back, 0, logE.dim)))      # alpha_t beta_t
+            acc(P, g * _hmm_part(back, 2 * R * T * K, P.dim))
+            acc(pi, g * _hmm_part(back, 2 * R * T * K + K * K, pi.dim))
+        elif n.op == "hmm_part" or n.op in _HMMOPS:
+            raise NotImplementedError("second derivatives of the HMM stages (hmm_state_prob carries no gradient)")
         elif n.op in _STAGES:
             raise NotImplementedError("second derivatives of the matrix and scan stages")
         else:
@@ -1125,6 +1241,35 @@ def _np_scan(op: str, args: list[np.ndarray], R: int, T: int, N: int) -> np.ndar
             lam = a[:, :, t + 1] * lam + b[:, :, t]
             out[:, :, t] = lam
     return out.reshape(N, R * T)
+
+
+def _np_hmm(op: str, args: list[np.ndarray], R: int, T: int, K: int, N: int) -> np.ndarray:
+    """the packed result of the forward (``hmm_fwd``) or backward (``hmm_bwd``) stage by the plain scaled algorithm: the checker (the
+    bitwise reference of the device routines is tests/fixtures/hmm_reference.c)"""
+    def full(v, n):
+        return np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, n))
+
+    logE, P = full(args[0], R * T * K).reshape(N, R, T, K), full(args[1], K * K).reshape(N, K, K)
+    if op == "hmm_fwd":
+        pi = full(args[2], K)
+        alpha, c = np.empty((N, R, T, K)), np.empty((N, R, T))
+        m = logE.max(axis=3)
+        e = np.exp(logE - m[..., None])
+        for t in range(T):
+            a = (pi[:, None, :] if t == 0 else np.einsum("nri,nij->nrj", alpha[:, :, t - 1], P)) * e[:, :, t]
+            c[:, :, t] = a.sum(axis=2)
+            alpha[:, :, t] = a / c[:, :, t, None]
+        return np.concatenate([alpha.reshape(N, -1), c.reshape(N, -1), m.reshape(N, -1)], axis=1)
+    F = args[2]
+    alpha, c, m = F[:, :R * T * K].reshape(N, R, T, K), F[:, R * T * K:R * T * K + R * T].reshape(N, R, T), F[:, R * T * K + R * T:].reshape(N, R, T)
+    e = np.exp(logE - m[..., None])
+    beta, w = np.ones((N, R, T, K)), np.empty((N, R, T, K))
+    for t in range(T - 1, -1, -1):
+        w[:, :, t] = e[:, :, t] * beta[:, :, t] / c[:, :, t, None]
+        if t:
+            beta[:, :, t - 1] = np.einsum("nij,nrj->nri", P, w[:, :, t])
+    Pbar = np.einsum("nrti,nrtj->nij", alpha[:, :, :-1], w[:, :, 1:])
+    return np.concatenate([beta.reshape(N, -1), w.reshape(N, -1), Pbar.reshape(N, -1), w[:, :, 0].sum(axis=1)], axis=1)
 
 
 def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.ndarray]:
@@ -1220,6 +1365,13 @@ def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.
                 v = _np_matop(n.op, args, *n.payload)
             elif n.op in _SCANOPS:
                 v = _np_scan(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
+            elif n.op in _HMMOPS:
+                v = _np_hmm(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
+            elif n.op == "hmm_part":
+                v = a[:, n.payload:n.payload + dim_len(n.dim)]
+            elif n.op == "hmm_ll":
+                R, T, K = n.payload
+                v = np.log(a[:, R * T * K:R * T * K + R * T]) + a[:, R * T * K + R * T:]
             elif n.op == "rhscol":
                 R = n.args[0].dim.factors[1].size
                 v = np.broadcast_to(a[:, None] if a.ndim == 1 else a, (N, dim_len(n.args[0].dim))).reshape(N, -1, R)[:, :, n.payload]
@@ -1241,6 +1393,17 @@ def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.
 
 
 # --------------------------------------------------------------------------- code generation
+def _series_lengths(nodes) -> set[int]:
+    """the lengths of the dimensions the series of the forward-backward stages among ``nodes`` live on: steps x states, steps, time
+    (by length, not by name: a traced model has its own dimension per tensor)"""
+    sizes: set[int] = set()
+    for n in nodes:
+        if n.op in _HMMOPS:
+            R, T, K = n.payload[:3]
+            sizes |= {R * T * K, R * T, T}
+    return sizes
+
+
 class _Out:
     """Where a generated function writes one of its outputs: what ``_Gen`` reads of a parameter node (``dim``, ``payload`` = offset
     or (offset, valid length)), for outputs that are not gradients — the rows of the generated expand function.  ``perm`` =
@@ -1277,6 +1440,11 @@ class _Gen:
         # names in the generated source count the nodes of THIS graph (node ids count every node ever made: the same model built
         # twice would print two different sources, and the library cache is keyed by the source)
         self.num: dict[int, int] = {n.id: k for k, n in enumerate(self.order)}
+        # Loops over the dimensions of a forward-backward stage's series (those as long as steps x states, steps or time) are unrolled
+        # _UNROLL times whatever that length, as loops over a data dimension are: the length of a series then changes constants of the
+        # source and nothing else.  The loop bounds are constants, so the compiler drops the iterations a short series never reaches.
+        # Other loops, and so other models, keep their source byte for byte.
+        self.even_unroll: set[int] = set(getattr(model, "_hmm_lengths", ())) | _series_lengths(self.order)
         self.level: dict[int, int] = {}
         for n in self.order:
             lv = max([self.level[a.id] for a in n.args], default=0)
@@ -1287,8 +1455,8 @@ class _Gen:
         # segment sums (stored grouped by target) ...
         self.stored: dict[Any, tuple[str, Dim]] = {}
         for n in self.order:
-            if n.op in ("gather", "pad", "trunc") and n.args[0].op not in ("vparam", "data"):
-                self.stored[n.args[0].id] = ("plain", n.args[0].dim)
+            if n.op in ("gather", "pad", "trunc") and n.args[0].op not in ("vparam", "data", "rowpack"):
+                self.stored[n.args[0].id] = ("plain", n.args[0].dim)     # (a rowpack is stored already, by its rows' loop: below)
             elif n.op == "segsum":
                 self.stored[("seg", n.args[0].id, n.payload.name)] = ("grouped", n.args[0].dim)
             elif n.op == "elem" and n.args[0].op not in ("vparam", "data", "stack"):
@@ -1326,7 +1494,7 @@ class _Gen:
                 if n.op == "segsum":
                     evaluated.setdefault(n.id, set()).add(lv[1])
                     continue               # (its argument was stored by an earlier loop)
-                if n.op in ("gather", "pad", "trunc", "rhscol"):
+                if n.op in ("gather", "pad", "trunc", "rhscol", "hmm_part", "hmm_ll"):
                     continue
                 stack.extend(n.args)
         for nid, levels in evaluated.items():
@@ -1347,13 +1515,19 @@ class _Gen:
                 seen.add(n.id)
                 if n.op == "vparam":
                     reads.setdefault(n.id, set()).add(key)
-                if n.op in ("stack", "gather", "segsum", "pad", "trunc", "rhscol", "rowpack") + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
+                if n.op in ("stack", "gather", "segsum", "pad", "trunc", "rhscol", "rowpack", "hmm_part", "hmm_ll") + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
                     continue
                 stack.extend(n.args)
         for nid, loops in reads.items():
             d = by_id[nid].dim
             if len(loops) > 1 and d.size is not None and d.size <= self.threads * _UNROLL:
                 self.hoisted.add(nid)
+
+    def unroll(self, d: Dim) -> int:
+        """how many iterations of a loop over ``d`` are written side by side"""
+        if d.size is None or d.size in self.even_unroll:
+            return _UNROLL
+        return max(1, min(_UNROLL, -(-d.size // self.threads)))
 
     def loop_roots(self) -> dict[tuple[int, int], list[Expr]]:
         """(id of the dimension, level) -> the nodes the loop has to produce: arguments of sums, stored values, gradient rows"""
@@ -1395,6 +1569,8 @@ class _Gen:
             emit('#include "chain_scan.h"')
         if any(n.op in _MVOPS for n in self.order):
             emit('#include "chain_matvec.h"')
+        if any(n.op in _HMMOPS for n in self.order):
+            emit('#include "chain_hmm.h"')
         emit(f"__device__ double {self.fn_name}(const NphipData& data, int dim, const double* x, double* g, double* lds, const double* shared, int lane) {{")
         # dimension lengths, data pointers (shared LDS where staged, else global), LDS scratch
         for d in m._dims.values():
@@ -1429,8 +1605,7 @@ class _Gen:
         for nid in sorted(self.hoisted):
             n = by_id_[nid]
             off, nv = n.payload
-            U = max(1, min(_UNROLL, -(-n.dim.size // self.threads)))
-            for u in range(U):
+            for u in range(self.unroll(n.dim)):
                 idx = f"(lane + {self.threads * u})"
                 emit(f"    const double H{self.num[nid]}_{u} = ({idx} < {nv}) ? x[{off} + {idx}] : 0.0;")
         max_level = max(self.level.values(), default=0)
@@ -1470,7 +1645,7 @@ class _Gen:
                 emit("    nphip_chain_barrier();")
             for n in self.order:
                 if n.op in _STAGES and self.level[n.id] == lv:
-                    emit(self.matop_call(n) if n.op in _MATOPS else self.scan_call(n) if n.op in _SCANOPS else self.mv_call(n))
+                    emit(self.matop_call(n) if n.op in _MATOPS else self.scan_call(n) if n.op in _SCANOPS else self.hmm_call(n) if n.op in _HMMOPS else self.mv_call(n))
                     if n.op in _MVOPS:
                         mark(f"stage {n.op}<{n.payload[1]}, {n.payload[2]}> of {n.payload[0]}")
             mark(f"scalars of level {lv}")
@@ -1549,6 +1724,19 @@ class _Gen:
             return f"    nphip_mv::times<{K}, {R}>(data.{name}__t, {arg}, {out}, n_{rows.name}, lane);"
         return f"    nphip_mv::times_t<{K}, {R}>(data.{name}, {arg}, {out}, n_{rows.name}, lane);"
 
+    # ---- HMM stages (csrc/chain_hmm.h; every routine ends with the chain's barrier)
+    def hmm_call(self, n: Expr) -> str:
+        R, T, K = n.payload
+        args = ", ".join(self.store_name[a.id] for a in n.args)
+        out = self.store_name[n.id]
+        if n.op == "hmm_fwd":
+            return f"    nphip_hmm::forward<{R}, {T}, {K}>({args}, {out}, lane);"
+        call = f"    nphip_hmm::backward<{R}, {T}, {K}>({args}, {out}, lane);"
+        if any(m.op == "hmm_part" and m.args[0] is n and m.payload >= 2 * R * T * K for m in self.order):
+            # (the adjoints of P and pi: the density's gradient reads them, the smoothed probabilities of the expand function do not)
+            call += f" nphip_hmm::transition_adjoint<{R}, {T}, {K}>({self.store_name[n.args[2].id]}, {out}, lane);"
+        return call
+
     # ---- scalars
     def sref(self, n: Expr) -> str:
         if n.op == "const":
@@ -1586,7 +1774,7 @@ class _Gen:
     def loop(self, d: Dim, lv: int, sums, stores, outs, mark=lambda label: None):
         emit = self.L.append
         T = self.threads
-        U = _UNROLL if d.size is None else max(1, min(_UNROLL, -(-d.size // T)))
+        U = self.unroll(d)
         by_id = {n.id: n for n in self.order}
         emit(f"    // level {lv}, over {d.name}")
         for n in sums:
@@ -1622,6 +1810,13 @@ class _Gen:
                 elif n.op == "rhscol":
                     src = n.args[0]
                     stages[0].append(f"        const double {name} = {self.store_name[src.id]}[j_{u} * {src.dim.factors[1].size} + {n.payload}];")
+                elif n.op == "hmm_part":
+                    stages[0].append(f"        const double {name} = {self.store_name[n.args[0].id]}[{n.payload} + j_{u}];")
+                elif n.op == "hmm_ll":
+                    R_, T_, K_ = n.payload
+                    arr = self.store_name[n.args[0].id]
+                    stages[0].append(f"        const double {name}_c = {arr}[{R_ * T_ * K_} + j_{u}], {name}_m = {arr}[{R_ * T_ * K_ + R_ * T_} + j_{u}];")
+                    stages[3].append(f"        const double {name} = log({name}_c) + {name}_m;")
                 elif n.op == "gather":
                     src, index = n.args[0], n.payload
                     iname = f"k{index.name}_{u}"
@@ -2099,6 +2294,28 @@ class Model:
         L = stack([ent.get((i, j), Expr.const(0.0)) for i in range(k) for j in range(k)], prod)
         return L, stack(sds, kd)
 
+    def transition_matrix(self, name: str, K: int, concentration: float | None = None) -> Expr:
+        """The K x K transition matrix of a hidden Markov model: K simplex parameters ``name_0 .. name_{K-1}`` on ``name + "_k"``, one
+        per row (the simplex transform and its Jacobian: ``name_i_simplex__`` are the unconstrained names), each with a
+        ``dirichlet_lpdf(row, concentration)`` prior when a concentration is given.  Returns the matrix on ``product(name + "_k",
+        name + "_k")`` (row-major: row i the distribution of the next state given state i) and reports it under ``name``."""
+        k = int(K)
+        kd = self.dim(name + "_k", k)
+        rows = [self.param(f"{name}_{i}", dim=kd.name, simplex=True) for i in range(k)]
+        if concentration is not None:
+            for row in rows:
+                self.add_logp(dirichlet_lpdf(row, concentration))
+        prod = self.product(kd.name, kd.name)
+        if k == 1:
+            P = _bcast(elem(rows[0], 0), prod)
+        else:
+            # pack_columns puts row i of the matrix into COLUMN i; the transposing gather turns it over
+            e = np.arange(k * k)
+            turn = self._add_index(f"{name}__turn", (e % k) * k + e // k, prod.name, prod.name)
+            P = pack_columns(rows, prod)[turn]
+        self.deterministic(name, P)
+        return P
+
     def data(self, name: str, values, dim: str | None = None) -> Expr:
         """Observed / shared data: a float array over ``dim`` or (``dim=None``) one float.  ``with_data`` can replace it."""
         self._check_new_data(name)
@@ -2423,6 +2640,10 @@ class Model:
             if waves_per_chain not in (None, 1):
                 raise ValueError("a model with matrix stages (cholesky / solve_lower) runs with waves_per_chain=1")
             waves_per_chain = 1
+        hmms = [n for n in _topo([logp] + grads + [e for _, e in self._det]) if n.op in _HMMOPS]
+        if hmms and max(n.payload[2] for n in hmms) > MAX_HMM_STATES:
+            raise ValueError(f"a compiled density sums out up to {MAX_HMM_STATES} hidden states (this model: {max(n.payload[2] for n in hmms)})")
+        self._hmm_lengths = _series_lengths(hmms)   # (the expand function's loops follow the same rule, whatever it reports)
         self._plan_staging([logp] + grads + [e for _, e in self._det])
         if waves_per_chain is None:
             for waves_per_chain in (1, 2, 4):
@@ -2552,7 +2773,7 @@ class Model:
         else:
             out_names, out_shapes = names, shapes
         egen = _Gen(self, Expr.const(0.0), [], waves_per_chain, outputs=offs, fn_name="nphip_expand") if (fixed and det) else None
-        if egen is not None and any(n.op in _SCANOPS + _MVOPS for n in egen.order):
+        if egen is not None and any(n.op in _SCANOPS + _MVOPS + _HMMOPS for n in egen.order):
             # (the generated expand keeps its arrays in LDS, (4 rows per workgroup with one wave per row) + the staged data: a long scan
             #  that does not fit is expanded on the host)
             rows_per_block = 4 if waves_per_chain == 1 else 1

@@ -9,6 +9,9 @@ through ``from_torchfunc``, or traced with :func:`nutpie_amd.torch_trace.trace`)
   ``s_0^2`` the sample variance; ``omega > 0``, ``alpha, beta`` in (0, 1).  Vector: ``[mu, omega_log__, alpha_interval__, beta_interval__]``.
 * :func:`ar1_latent_model` — a non-centred stationary AR(1) latent state ``x_t = phi x_{t-1} + sigma z_t`` (``x_0 = sigma z_0 /
   sqrt(1 - phi^2)``) observed with Normal noise ``tau``.  Vector: ``[phi_interval__, sigma_log__, tau_log__, z (T)]``.
+* :func:`regime_switching_model` — a Gaussian hidden Markov model (regime switching): the discrete state is summed out by the forward
+  algorithm (``symbolic.hmm_marginal_lpdf``); ordered state means, one scale, a transition matrix of simplex rows.
+  Vector: ``[mu_ordered__ (K), sigma_log__, P_0_simplex__ (K - 1), ..., P_{K-1}_simplex__ (K - 1)]``.
 """
 
 from __future__ import annotations
@@ -195,3 +198,80 @@ def ar1_latent_torch_density(y=None, device="cpu"):
         return lp - 0.5 * (r * r).sum(-1) - y.shape[0] * (lt + _HALF_LOG_2PI)
 
     return 3 + y_np.size, logp
+
+
+# --------------------------------------------------------------------------- regime switching (a Gaussian hidden Markov model)
+def synthetic_regimes(T: int = 200, K: int = 2, R: int = 1, stay: float = 0.9, sigma: float = 0.7, seed: int = 20261019) -> np.ndarray:
+    """R series of T observations from a sticky K-state chain (it keeps its state with probability ``stay``) with state means
+    ``3 (k - (K - 1) / 2)`` and Normal noise ``sigma``"""
+    rng = np.random.default_rng(seed)
+    means = 3.0 * (np.arange(K) - 0.5 * (K - 1))
+    y = np.empty((R, T))
+    for r in range(R):
+        z = rng.integers(K)
+        for t in range(T):
+            if t and K > 1 and rng.uniform() > stay:
+                z = (z + 1 + rng.integers(K - 1)) % K
+            y[r, t] = means[z] + sigma * rng.normal()
+    return y
+
+
+_REGIME_CONCENTRATION = 2.0
+
+
+def regime_switching_model(T: int = 200, K: int = 2, seed: int = 20261019, R: int = 1, y=None) -> S.Model:
+    """mu ~ Normal(0, 5) on the K states, ordered (the labels cannot switch); sigma ~ HalfNormal(2); every row of the transition
+    matrix P ~ Dirichlet(2) (``Model.transition_matrix``); the initial distribution uniform and constant; y_t ~ Normal(mu[z_t], sigma)
+    with the states z summed out: ``hmm_marginal_lpdf``.  ``R`` > 1: a panel of R independent series that share the parameters.
+    Deterministic ``state_prob``: the smoothed probability of every state at every step (``[R T, K]``)."""
+    y = np.asarray(synthetic_regimes(T, K, R, seed=seed) if y is None else y, dtype=np.float64).reshape(R, T)
+    m = S.Model()
+    mu = m.param("mu", dim="P_k", size=K, ordered=True, initval=3.0 * (np.arange(K) - 0.5 * (K - 1)))
+    sigma = m.param("sigma", lower=0.0)
+    P = m.transition_matrix("P", K, concentration=_REGIME_CONCENTRATION)
+    m.add_logp(S.normal_lpdf(mu, 0.0, 5.0).sum() + S.halfnormal_lpdf(sigma, 2.0))
+    if R == 1:
+        m.dim("time", T)
+        steps, along = "time", None
+    else:
+        m.dim("series", R)
+        m.dim("time", T)
+        steps, along = m.product("series", "time").name, "time"
+    obs = m.data("y", y.reshape(-1), dim=steps)
+    log_emission = S.normal_lpdf(m.broadcast(obs, steps, "P_k"), m.broadcast(mu, steps, "P_k"), sigma)
+    pi = m.data("initial", np.full(K, 1.0 / K), dim="P_k")
+    m.add_logp(S.hmm_marginal_lpdf(log_emission, P, pi, along=along))
+    m.deterministic("state_prob", S.hmm_state_prob(log_emission, P, pi, along=along))
+    return m
+
+
+def regime_switching_torch_density(T: int = 200, K: int = 2, seed: int = 20261019, R: int = 1, y=None, device="cpu"):
+    """The same log-density as :func:`regime_switching_model` with :func:`nutpie_amd.torch_trace.hmm_marginal`.  Returns ``(D, logp)``."""
+    import torch
+
+    from nutpie_amd.torch_trace import hmm_marginal
+
+    y_np = np.asarray(synthetic_regimes(T, K, R, seed=seed) if y is None else y, dtype=np.float64).reshape(R, T)
+    dev = torch.device(device) if isinstance(device, str) else torch.device("cuda", device)
+    obs = torch.as_tensor(y_np, device=dev)
+    conc = _REGIME_CONCENTRATION
+    dirichlet_const = math.lgamma(K * conc) - K * math.lgamma(conc)
+
+    def logp(x):
+        raw_mu, ls, raw_p = x[:, :K], x[:, K], x[:, K + 1:].reshape(-1, K, K - 1)
+        mu = torch.cat([raw_mu[:, :1], raw_mu[:, :1] + torch.cumsum(torch.exp(raw_mu[:, 1:]), dim=-1)], dim=-1) if K > 1 else raw_mu
+        sigma = ls.exp()
+        lp = raw_mu[:, 1:].sum(-1) - (0.5 * (mu / 5.0) ** 2).sum(-1) - K * (math.log(5.0) + _HALF_LOG_2PI)
+        lp = lp + 0.5 * math.log(2.0 / math.pi) - math.log(2.0) - 0.5 * (sigma / 2.0) ** 2 + ls
+        # the simplex transform of every row (the softmax of the zero-sum extension of its free values) and its Jacobian
+        s = raw_p.sum(-1, keepdim=True)
+        z = torch.cat([raw_p + s, torch.zeros_like(s)], dim=-1)
+        lse = torch.logsumexp(z, dim=-1, keepdim=True)
+        log_rows = z - lse
+        lp = lp + (math.log(K) + K * s - K * lse).sum((-1, -2)) + (conc - 1.0) * log_rows.sum((-1, -2)) + K * dirichlet_const
+        r = (obs[None, :, :, None] - mu[:, None, None, :]) / sigma[:, None, None, None]
+        log_emission = -0.5 * r * r - ls[:, None, None, None] - _HALF_LOG_2PI
+        initial = torch.full((K,), 1.0 / K, dtype=x.dtype, device=x.device)
+        return lp + hmm_marginal(log_emission, torch.exp(log_rows)[:, None], initial).sum(-1)
+
+    return K + 1 + K * (K - 1), logp
