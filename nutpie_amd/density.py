@@ -199,6 +199,8 @@ def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verb
         deps.append(os.path.join(_CSRC, "chain_matvec.h"))
     if '#include "chain_hmm.h"' in user_source:
         deps.append(os.path.join(_CSRC, "chain_hmm.h"))
+    if '#include "chain_kalman.h"' in user_source:
+        deps.extend(os.path.join(_CSRC, h) for h in ("chain_kalman.h", "chain_hmm.h"))     # (the Kalman header includes the HMM header's cross-lane moves)
     h = hashlib.sha256()
     h.update(src.encode())
     for d in deps:

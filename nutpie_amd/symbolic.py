@@ -38,6 +38,11 @@ scaled forward algorithm (Stan's ``hmm_marginal``), ``hmm_state_prob`` reports t
 ``m.transition_matrix(name, K, concentration)`` declares a K x K matrix of simplex rows — a stage between loops that one device
 routine runs on the chain's wave(s) (``csrc/chain_hmm.h``), K <= 16, up to four waves per chain.
 
+Linear Gaussian state-space models: ``kalman_marginal_lpdf(y, design=, obs_var=, transition=, state_cov=, init_mean=, init_cov=,
+observed=None, along=None)`` sums the latent state out with a Kalman filter, ``kalman_filtered_state`` reports the filtered or predicted
+state means — a stage between loops that one device routine runs on the chain's wave(s) (``csrc/chain_kalman.h``),
+state dimension <= 8, up to four waves per chain.
+
 Also: ``m.matrix("X", values, dim="obs", cols="coef")`` and ``X @ beta`` (a design matrix: with up to 63 columns lowered to a sum over
 its columns, the transposed product to one wave-wide sum per column; with more — or ``stage=True``, or a ``B`` with several right-hand
 sides on a ``product(coef, rhs)`` — a stage between loops that reads the matrix from L2, ``csrc/chain_matvec.h``, DESIGN.md §11.7,
@@ -76,7 +81,8 @@ __all__ = ["Model", "Expr", "Matrix", "exp", "log", "log1p", "sqrt", "softplus",
            "inverse_gamma_lpdf", "beta_lpdf", "laplace_lpdf", "logistic_lpdf", "weibull_lpdf", "uniform_lpdf",
            "bernoulli_logit_lpmf", "binomial_logit_lpmf", "negative_binomial_log_lpmf", "poisson_log_lpmf", "dirichlet_lpdf", "flat_lpdf",
            "cholesky", "solve_lower", "log_det_chol", "mvnormal_lpdf", "lkj_corr_cholesky_lpdf",
-           "linear_recurrence", "cumsum", "column", "pack_columns", "hmm_marginal_lpdf", "hmm_state_prob"]
+           "linear_recurrence", "cumsum", "column", "pack_columns", "hmm_marginal_lpdf", "hmm_state_prob",
+           "kalman_marginal_lpdf", "kalman_filtered_state"]
 
 _WAVE = 64
 _SEG_BATCH = os.environ.get("NUTPIE_AMD_SEG_MODE", "select") != "loop"   # (developer switch: "loop" = plain loops over a segment)
@@ -645,7 +651,15 @@ def pack_columns(columns, dim: Dim) -> Expr:
 # reads of the stored array, like ``rhscol``.  payload = (R, T, K).
 _HMMOPS = ("hmm_fwd", "hmm_bwd")
 MAX_HMM_STATES = 16   # a lane keeps its column (row) of the transition matrix in registers, a group of up to 16 lanes owns a series
-_STAGES = _MATOPS + _SCANOPS + _MVOPS + _HMMOPS
+# Kalman filter stages (csrc/chain_kalman.h): ``kalman_fwd`` (args y, Z, h, Tm, Q, a0, P0 [, obs]) is the filter, ``kalman_bwd`` (args y, Z,
+# h, Tm, Q, the forward result, vbar, Fbar [, obs]) its adjoint — what the gradient emits, with the adjoints of the stored v and F that
+# the IR's own loops compute as stored operands.  Each packs its arrays on a dimension of its own: [apred: R T m | Ppred: R T m m |
+# afilt: R T m | v: R T | F: R T] resp. [ybar: R T | hbar: R T | Zbar: R T m | Tbar: m m | Qbar: m m | a0bar: m | P0bar: m m |
+# per-series partials: R (3 m m + m)]; ``kalman_part`` (payload: the offset) reads one of them as a value on the dimension it belongs
+# to, like ``hmm_part``.  payload = (R, T, m, masked).
+_KALOPS = ("kalman_fwd", "kalman_bwd")
+MAX_KALMAN_STATE = 8   # a lane keeps its row of the state covariance in registers, a group of up to 8 lanes owns a series
+_STAGES = _MATOPS + _SCANOPS + _MVOPS + _HMMOPS + _KALOPS
 
 
 def _scan(a, b, init, R: int, T: int, rows: Dim | None = None) -> Expr:
@@ -807,6 +821,126 @@ def hmm_state_prob(log_emission, transition, initial, along: str | None = None, 
     the arrays the density computes anyway.  It carries no gradient."""
     logE, R, T, K, steps = _hmm_shape(log_emission, along, "hmm_state_prob")
     return _hmm_prob(_hmm_forward(logE, transition, initial, R, T, K, steps, "hmm_state_prob"), bool(smoothed))
+
+
+# --------------------------------------------------------------------------- linear Gaussian state-space models
+def _kalman_sizes(R: int, T: int, m: int) -> tuple[int, int]:
+    return R * T * (2 * m + m * m + 2), R * T * (2 + m) + 3 * m * m + m + R * (3 * m * m + m)
+
+
+def _kalman_forward(y, Z, h, Tm, Q, a0, P0, obs, R: int, T: int, m: int, what: str = "kalman_marginal_lpdf") -> Expr:
+    """the filter stage for ``y`` on a dimension of R T elements, ``Z`` on one of R T m (row-major), ``h`` on that of ``y`` — what a front
+    end that keeps its tensors flat calls (the torch tracer); the public functions are this on the dimensions of a ``Model``"""
+    y, Z, h, Tm, Q, a0, P0 = (Expr.wrap(v) for v in (y, Z, h, Tm, Q, a0, P0))
+    steps = y.dim
+    if steps is None or steps.size is None or steps.size != R * T:
+        raise ValueError(f"{what}: y is a value or data on a fixed-size dimension (R series of T steps)")
+    if Z.dim is None or Z.dim.size != R * T * m:
+        raise ValueError(f"{what}: design is a value on the {m} states or on product(steps, state)")
+    for name, v in (("transition", Tm), ("state_cov", Q), ("init_cov", P0)):
+        if v.dim is None or v.dim.size != m * m:
+            raise ValueError(f"{what}: {name} is an m x m value on a fixed-size dimension (m = {m}: the states of design)")
+    if a0.dim is None or a0.dim.size != m:
+        raise ValueError(f"{what}: init_mean is a scalar or a value on the {m} states")
+    if h.dim is not steps:
+        raise ValueError(f"{what}: obs_var is a scalar or a value on the dimension of y")
+    if obs is not None and (obs.op != "data" or obs.dim is not steps):
+        raise ValueError(f"{what}: observed is data (0 or 1) on the dimension of y")
+    model = steps._model() if steps._model is not None else None
+    if model is None:
+        raise ValueError(f"{what}: y lives on a dimension of no Model")
+    n_f, n_b = _kalman_sizes(R, T, m)
+    # (a second filter over the same steps with another split into series or another state: dimensions named after its shape)
+    tag = "" if model._dims.get(f"{steps.name}__kf_f", Dim("", n_f)).size == n_f and model._dims.get(f"{steps.name}__kf_b", Dim("", n_b)).size == n_b \
+        else f"_{R}x{T}x{m}"
+    packed = model.dim(f"{steps.name}__kf_f{tag}", n_f)
+    packed._kalman_back = model.dim(f"{steps.name}__kf_b{tag}", n_b)
+    args = (y, Z, h, Tm, Q, a0, P0) + ((obs,) if obs is not None else ())
+    return Expr("kalman_fwd", args, packed, (int(R), int(T), int(m), obs is not None))
+
+
+def _kalman_backward(F: Expr, vbar: Expr, Fbar: Expr) -> Expr:
+    y, Z, h, Tm, Q = F.args[:5]
+    return Expr("kalman_bwd", (y, Z, h, Tm, Q, F, vbar, Fbar) + F.args[7:], F.dim._kalman_back, F.payload)
+
+
+def _kalman_part(X: Expr, offset: int, dim: Dim) -> Expr:
+    return Expr("kalman_part", (X,), dim, int(offset))
+
+
+def _kalman_terms(F: Expr) -> Expr:
+    """the steps' -1/2 obs (log 2 pi + log F + v^2 / F): element-wise IR on the stored v and F"""
+    R, T, m, masked = F.payload
+    steps = F.args[0].dim
+    o = R * T * (2 * m + m * m)
+    v, Fv = _kalman_part(F, o, steps), _kalman_part(F, o + R * T, steps)
+    terms = (2.0 * _HALF_LOG_2PI) + log(Fv) + v * v / Fv
+    if masked:
+        terms = F.args[7] * terms
+    return -0.5 * terms
+
+
+def _kalman_args(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed, along, what: str):
+    y, Z, h, a0 = Expr.wrap(y), Expr.wrap(design), Expr.wrap(obs_var), Expr.wrap(init_mean)
+    steps = y.dim
+    if steps is None or steps.size is None:
+        raise ValueError(f"{what}: y is a value or data on a fixed-size dimension (steps, or product(series, steps))")
+    if along is None or (steps.factors is None and along == steps.name):
+        R, T = 1, steps.size
+    elif steps.factors is None:
+        raise ValueError(f"{what}: along={along!r} names no axis of dimension {steps.name!r}")
+    else:
+        series, time = steps.factors
+        if along == series.name and along != time.name:
+            raise ValueError(f"{what}: {along!r} is the outer axis of {steps.name!r}; the time axis must be the inner (second) one")
+        if along != time.name:
+            raise ValueError(f"{what}: along={along!r} names no axis of dimension {steps.name!r}")
+        R, T = series.size, time.size
+    model = steps._model() if steps._model is not None else None
+    if model is None or Z.dim is None or Z.dim.size is None:
+        raise ValueError(f"{what}: design is a value on the states or on product(steps, state), y lives on a dimension of a Model")
+    if Z.dim.factors is not None and Z.dim.factors[0] is steps:
+        state = Z.dim.factors[1]
+    elif Z.dim.factors is None:
+        state = Z.dim
+        Z = model.broadcast(Z, steps.name, state.name)
+    else:
+        raise ValueError(f"{what}: design is a value on the states or on product({steps.name!r}, state)")
+    if state.size is None:
+        raise ValueError(f"{what}: the state dimension has a fixed size")
+    if h.dim is None:
+        h = _bcast(h, steps)
+    if a0.dim is None:
+        a0 = _bcast(a0, state)
+    obs = None if observed is None else Expr.wrap(observed)
+    return y, Z, h, transition, state_cov, a0, init_cov, obs, R, T, state.size, state
+
+
+def kalman_marginal_lpdf(y, *, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None, along: str | None = None) -> Expr:
+    """The log-likelihood of a linear Gaussian state-space model with its state summed out by a Kalman filter:
+    ``state_0 ~ N(init_mean, init_cov)`` (before the first observation), ``y_t ~ N(design_t . state_t, obs_var_t)``,
+    ``state_{t+1} ~ N(transition state_t, state_cov)``; the value is ``-1/2 sum observed (log 2 pi + log F_t + v_t^2 / F_t)`` with the
+    innovations v and their variances F.  ``y``: a value or data on ``steps`` — one series — or on ``product(series, steps)`` with
+    ``along`` naming the inner (time) axis: every series its own filter with the same parameters, the values summed; an observation
+    offset is ``y - d``.  ``design``: a value on ``product(y.dim, state)`` or on ``state`` alone (the same row at every step);
+    ``obs_var``: a scalar or a value on ``y.dim``; ``transition``, ``state_cov``, ``init_cov``: m x m on fixed-size dimensions
+    (row-major); ``init_mean``: a scalar or a value on ``state``.  ``observed``: data on ``y.dim``, 0 where the observation is
+    missing (the step then only predicts).  m <= 8.  The covariances are used as given (not symmetrised), and the gradient is that of
+    what is evaluated.  A step with F <= 0 or a non-finite input makes the density NaN (a divergence; not guarded)."""
+    *args, R, T, m, _ = _kalman_args(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed, along, "kalman_marginal_lpdf")
+    return _kalman_terms(_kalman_forward(*args, R, T, m)).sum()
+
+
+def kalman_filtered_state(y, *, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None, along: str | None = None,
+                          predicted: bool = False) -> Expr:
+    """The mean of the state at every step given the observations up to and including the step (``predicted``: up to the step before),
+    a value on ``product(y.dim, state)``.  Meant for ``Model.deterministic``: with the same arguments as the model's
+    ``kalman_marginal_lpdf`` it reads the arrays the density computes anyway.  It carries no gradient."""
+    *args, R, T, m, state = _kalman_args(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed, along, "kalman_filtered_state")
+    F = _kalman_forward(*args, R, T, m, what="kalman_filtered_state")
+    steps = F.args[0].dim
+    out = steps._model().product(steps.name, state.name)
+    return _kalman_part(F, 0 if predicted else R * T * (m + m * m), out)
 
 
 def stack(scalars, dim: Dim) -> Expr:
@@ -1027,7 +1161,17 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
         adj[target.id] = adj[target.id] + e if target.id in adj else e
 
     elem_adj: dict[int, dict[int, Expr]] = {}     # vector -> {element: adjoint of elem(vector, element)}
+    kal_adj: dict[int, dict[str, Expr]] = {}      # Kalman filter stage -> the adjoints of its stored v and F
     for n in reversed(order):
+        if n.id in kal_adj:       # every consumer of the filter has been visited: its adjoint is one backward stage
+            parts = kal_adj.pop(n.id)
+            R, T, m, _ = n.payload
+            y, Z, h, Tm, Q, a0, P0 = n.args[:7]
+            back = _kalman_backward(n, *(_bcast(parts.get(k, Expr.const(0.0)), y.dim) for k in ("v", "F")))
+            for target, off in ((y, 0), (h, R * T), (Z, 2 * R * T), (Tm, R * T * (2 + m)), (Q, R * T * (2 + m) + m * m),
+                                (a0, R * T * (2 + m) + 2 * m * m), (P0, R * T * (2 + m) + 2 * m * m + m)):
+                acc(target, _kalman_part(back, off, target.dim))
+            continue
         if n.id in elem_adj:      # every consumer of n has been visited: the adjoints of its extracted elements as one vector
             parts = elem_adj.pop(n.id)
             acc(n, stack([parts.get(c, Expr.const(0.0)) for c in range(n.dim.size)], n.dim))
@@ -1147,6 +1291,14 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
             acc(logE, g * (_hmm_part(a, 0, logE.dim) * _hmm_part(back, 0, logE.dim)))      # alpha_t beta_t
             acc(P, g * _hmm_part(back, 2 * R * T * K, P.dim))
             acc(pi, g * _hmm_part(back, 2 * R * T * K + K * K, pi.dim))
+        elif n.op == "kalman_part" and a.op == "kalman_fwd" and n.payload >= a.payload[0] * a.payload[1] * (2 * a.payload[2] + a.payload[2] ** 2):
+            R, T, m, _ = a.payload
+            which = "v" if n.payload == R * T * (2 * m + m * m) else "F"
+            slot = kal_adj.setdefault(a.id, {})
+            g = _bcast(g, d)
+            slot[which] = slot[which] + g if which in slot else g
+        elif n.op == "kalman_part" or n.op in _KALOPS:
+            raise NotImplementedError("second derivatives of the Kalman filter stages (kalman_filtered_state carries no gradient)")
         elif n.op == "hmm_part" or n.op in _HMMOPS:
             raise NotImplementedError("second derivatives of the HMM stages (hmm_state_prob carries no gradient)")
         elif n.op in _STAGES:
@@ -1272,6 +1424,69 @@ def _np_hmm(op: str, args: list[np.ndarray], R: int, T: int, K: int, N: int) -> 
     return np.concatenate([beta.reshape(N, -1), w.reshape(N, -1), Pbar.reshape(N, -1), w[:, :, 0].sum(axis=1)], axis=1)
 
 
+def _np_kalman(op: str, args: list[np.ndarray], R: int, T: int, m: int, masked: bool, N: int) -> np.ndarray:
+    """the packed result of the filter (``kalman_fwd``) or its adjoint (``kalman_bwd``) by the plain sequential algorithm in matrix form,
+    in the precision of its arguments: the checker (the bitwise reference of the device routines is tests/fixtures/kalman_reference.c)"""
+    dt = np.result_type(*args)
+
+    def full(v, *shape):
+        v = np.asarray(v)
+        return np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, int(np.prod(shape)))).reshape(N, *shape)
+
+    y, Z, h, Tm, Q = full(args[0], R, T), full(args[1], R, T, m), full(args[2], R, T), full(args[3], m, m), full(args[4], m, m)
+    fwd = op == "kalman_fwd"
+    obs = full(args[7 if fwd else 8], R, T) != 0 if masked else np.ones((N, R, T), bool)
+    if fwd:
+        a = np.broadcast_to(full(args[5], m)[:, None], (N, R, m)).astype(dt)
+        P = np.broadcast_to(full(args[6], m, m)[:, None], (N, R, m, m)).astype(dt)
+        apred, Ppred, afilt = np.empty((N, R, T, m), dt), np.empty((N, R, T, m, m), dt), np.empty((N, R, T, m), dt)
+        vs, Fs = np.empty((N, R, T), dt), np.empty((N, R, T), dt)
+        for t in range(T):
+            z, seen = Z[:, :, t], obs[:, :, t]
+            apred[:, :, t], Ppred[:, :, t] = a, P
+            M = np.einsum("nrij,nrj->nri", P, z)
+            v = np.where(seen, y[:, :, t] - np.einsum("nrk,nrk->nr", z, a), 0.0)
+            Fv = np.where(seen, h[:, :, t] + np.einsum("nrk,nrk->nr", z, M), 1.0)
+            K = np.where(seen[..., None], M / Fv[..., None], 0.0)
+            af = a + K * v[..., None]
+            Pf = P - K[..., :, None] * M[..., None, :]
+            vs[:, :, t], Fs[:, :, t], afilt[:, :, t] = v, Fv, af
+            a = np.einsum("nik,nrk->nri", Tm, af)
+            P = Q[:, None] + np.einsum("nik,nrkl,njl->nrij", Tm, Pf, Tm)
+        return np.concatenate([v_.reshape(N, -1) for v_ in (apred, Ppred, afilt, vs, Fs)], axis=1)
+    F = np.asarray(args[5])
+    cuts = np.cumsum([R * T * m, R * T * m * m, R * T * m, R * T])
+    apred, Ppred, _, vs, Fs = (v_.reshape(N, R, T, *sh) for v_, sh in zip(np.split(F, cuts, axis=1), ((m,), (m, m), (m,), (), ())))
+    vbar, Fbar = full(args[6], R, T), full(args[7], R, T)
+    ybar, hbar, Zbar = np.zeros((N, R, T), dt), np.zeros((N, R, T), dt), np.zeros((N, R, T, m), dt)
+    Tb, Qb = np.zeros((N, R, m, m), dt), np.zeros((N, R, m, m), dt)
+    ab, Pb = np.zeros((N, R, m), dt), np.zeros((N, R, m, m), dt)
+    for t in range(T - 1, -1, -1):
+        z, seen, a, P, v, Fv = Z[:, :, t], obs[:, :, t], apred[:, :, t], Ppred[:, :, t], vs[:, :, t], Fs[:, :, t]
+        M = np.einsum("nrij,nrj->nri", P, z)
+        K = np.where(seen[..., None], M / Fv[..., None], 0.0)
+        af = a + K * v[..., None]
+        Pf = P - K[..., :, None] * M[..., None, :]
+        if t < T - 1:
+            Qb = Qb + Pb
+            Tb = Tb + np.einsum("nrij,njl,nrkl->nrik", Pb, Tm, Pf) + np.einsum("nrji,njl,nrlk->nrik", Pb, Tm, Pf) + ab[..., :, None] * af[..., None, :]
+            Pfb = np.einsum("nli,nrlj,njk->nrik", Tm, Pb, Tm)
+            afb = np.einsum("nik,nri->nrk", Tm, ab)
+        else:
+            Pfb, afb = np.zeros_like(Pb), np.zeros_like(ab)
+        Kb = afb * v[..., None] - np.einsum("nrij,nrj->nri", Pfb, M)
+        vb = vbar[:, :, t] + np.einsum("nri,nri->nr", afb, K)
+        Fb = Fbar[:, :, t] - np.einsum("nri,nri->nr", Kb, K) / Fv
+        Mb = -np.einsum("nrij,nri->nrj", Pfb, K) + Kb / Fv[..., None] + Fb[..., None] * z
+        s3, s4 = seen[..., None], seen[..., None, None]
+        ybar[:, :, t], hbar[:, :, t] = np.where(seen, vb, 0.0), np.where(seen, Fb, 0.0)
+        Zbar[:, :, t] = np.where(s3, Fb[..., None] * M + np.einsum("nrik,nri->nrk", P, Mb) - vb[..., None] * a, 0.0)
+        ab = np.where(s3, afb - vb[..., None] * z, afb)
+        Pb = np.where(s4, Pfb + Mb[..., :, None] * z[..., None, :], Pfb)
+    parts = np.concatenate([Tb.reshape(N, R, -1), Qb.reshape(N, R, -1), ab, Pb.reshape(N, R, -1)], axis=2)
+    return np.concatenate([ybar.reshape(N, -1), hbar.reshape(N, -1), Zbar.reshape(N, -1), parts.sum(axis=1), parts.reshape(N, -1)], axis=1)
+
+
 def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.ndarray]:
     """Values of ``nodes`` for a block of positions ``x[N, D]``: scalars as ``[N]``, dimensioned nodes as ``[N, len]``."""
     x = np.atleast_2d(np.asarray(x, dtype=np.float64))
@@ -1367,7 +1582,9 @@ def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.
                 v = _np_scan(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
             elif n.op in _HMMOPS:
                 v = _np_hmm(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
-            elif n.op == "hmm_part":
+            elif n.op in _KALOPS:
+                v = _np_kalman(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
+            elif n.op in ("hmm_part", "kalman_part"):
                 v = a[:, n.payload:n.payload + dim_len(n.dim)]
             elif n.op == "hmm_ll":
                 R, T, K = n.payload
@@ -1401,6 +1618,9 @@ def _series_lengths(nodes) -> set[int]:
         if n.op in _HMMOPS:
             R, T, K = n.payload[:3]
             sizes |= {R * T * K, R * T, T}
+        elif n.op in _KALOPS:
+            R, T, m = n.payload[:3]
+            sizes |= {R * T * m, R * T, T}
     return sizes
 
 
@@ -1494,7 +1714,7 @@ class _Gen:
                 if n.op == "segsum":
                     evaluated.setdefault(n.id, set()).add(lv[1])
                     continue               # (its argument was stored by an earlier loop)
-                if n.op in ("gather", "pad", "trunc", "rhscol", "hmm_part", "hmm_ll"):
+                if n.op in ("gather", "pad", "trunc", "rhscol", "hmm_part", "hmm_ll", "kalman_part"):
                     continue
                 stack.extend(n.args)
         for nid, levels in evaluated.items():
@@ -1515,7 +1735,7 @@ class _Gen:
                 seen.add(n.id)
                 if n.op == "vparam":
                     reads.setdefault(n.id, set()).add(key)
-                if n.op in ("stack", "gather", "segsum", "pad", "trunc", "rhscol", "rowpack", "hmm_part", "hmm_ll") + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
+                if n.op in ("stack", "gather", "segsum", "pad", "trunc", "rhscol", "rowpack", "hmm_part", "hmm_ll", "kalman_part") + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
                     continue
                 stack.extend(n.args)
         for nid, loops in reads.items():
@@ -1571,6 +1791,8 @@ class _Gen:
             emit('#include "chain_matvec.h"')
         if any(n.op in _HMMOPS for n in self.order):
             emit('#include "chain_hmm.h"')
+        if any(n.op in _KALOPS for n in self.order):
+            emit('#include "chain_kalman.h"')
         emit(f"__device__ double {self.fn_name}(const NphipData& data, int dim, const double* x, double* g, double* lds, const double* shared, int lane) {{")
         # dimension lengths, data pointers (shared LDS where staged, else global), LDS scratch
         for d in m._dims.values():
@@ -1645,7 +1867,9 @@ class _Gen:
                 emit("    nphip_chain_barrier();")
             for n in self.order:
                 if n.op in _STAGES and self.level[n.id] == lv:
-                    emit(self.matop_call(n) if n.op in _MATOPS else self.scan_call(n) if n.op in _SCANOPS else self.hmm_call(n) if n.op in _HMMOPS else self.mv_call(n))
+                    emit(self.matop_call(n) if n.op in _MATOPS else self.scan_call(n) if n.op in _SCANOPS else self.hmm_call(n) if n.op in _HMMOPS else self.kalman_call(n) if n.op in _KALOPS else self.mv_call(n))
+                    if n.op in _KALOPS:
+                        mark(f"stage {n.op}<{', '.join(str(int(v)) for v in n.payload)}>")
                     if n.op in _MVOPS:
                         mark(f"stage {n.op}<{n.payload[1]}, {n.payload[2]}> of {n.payload[0]}")
             mark(f"scalars of level {lv}")
@@ -1737,6 +1961,19 @@ class _Gen:
             call += f" nphip_hmm::transition_adjoint<{R}, {T}, {K}>({self.store_name[n.args[2].id]}, {out}, lane);"
         return call
 
+    # ---- Kalman filter stages (csrc/chain_kalman.h; every routine ends with the chain's barrier)
+    def kalman_call(self, n: Expr) -> str:
+        R, T, m, masked = n.payload
+        name = lambda a: self.store_name[a.id]      # noqa: E731
+        obs = name(n.args[-1]) if masked else "(const double*)nullptr"
+        shape = f"{R}, {T}, {m}, {'true' if masked else 'false'}"
+        if n.op == "kalman_fwd":
+            y, Z, h, Tm, Q, a0, P0 = n.args[:7]
+            return f"    nphip_kalman::forward<{shape}>({name(y)}, {obs}, {name(Z)}, {name(h)}, {name(Tm)}, {name(Q)}, {name(a0)}, {name(P0)}, {name(n)}, lane);"
+        y, Z, h, Tm, Q, F, vbar, Fbar = n.args[:8]
+        return (f"    nphip_kalman::backward<{shape}>({name(y)}, {obs}, {name(Z)}, {name(h)}, {name(Tm)}, {name(Q)}, {name(F)}, {name(vbar)}, {name(Fbar)}, "
+                f"{name(n)}, lane);")
+
     # ---- scalars
     def sref(self, n: Expr) -> str:
         if n.op == "const":
@@ -1810,7 +2047,7 @@ class _Gen:
                 elif n.op == "rhscol":
                     src = n.args[0]
                     stages[0].append(f"        const double {name} = {self.store_name[src.id]}[j_{u} * {src.dim.factors[1].size} + {n.payload}];")
-                elif n.op == "hmm_part":
+                elif n.op in ("hmm_part", "kalman_part"):
                     stages[0].append(f"        const double {name} = {self.store_name[n.args[0].id]}[{n.payload} + j_{u}];")
                 elif n.op == "hmm_ll":
                     R_, T_, K_ = n.payload
@@ -2643,7 +2880,10 @@ class Model:
         hmms = [n for n in _topo([logp] + grads + [e for _, e in self._det]) if n.op in _HMMOPS]
         if hmms and max(n.payload[2] for n in hmms) > MAX_HMM_STATES:
             raise ValueError(f"a compiled density sums out up to {MAX_HMM_STATES} hidden states (this model: {max(n.payload[2] for n in hmms)})")
-        self._hmm_lengths = _series_lengths(hmms)   # (the expand function's loops follow the same rule, whatever it reports)
+        kals = [n for n in _topo([logp] + grads + [e for _, e in self._det]) if n.op in _KALOPS]
+        if kals and max(n.payload[2] for n in kals) > MAX_KALMAN_STATE:
+            raise ValueError(f"a compiled density filters states of up to {MAX_KALMAN_STATE} dimensions (this model: {max(n.payload[2] for n in kals)})")
+        self._hmm_lengths = _series_lengths(hmms + kals)   # (the expand function's loops follow the same rule, whatever it reports)
         self._plan_staging([logp] + grads + [e for _, e in self._det])
         if waves_per_chain is None:
             for waves_per_chain in (1, 2, 4):
@@ -2773,7 +3013,7 @@ class Model:
         else:
             out_names, out_shapes = names, shapes
         egen = _Gen(self, Expr.const(0.0), [], waves_per_chain, outputs=offs, fn_name="nphip_expand") if (fixed and det) else None
-        if egen is not None and any(n.op in _SCANOPS + _MVOPS + _HMMOPS for n in egen.order):
+        if egen is not None and any(n.op in _SCANOPS + _MVOPS + _HMMOPS + _KALOPS for n in egen.order):
             # (the generated expand keeps its arrays in LDS, (4 rows per workgroup with one wave per row) + the staged data: a long scan
             #  that does not fit is expanded on the host)
             rows_per_block = 4 if waves_per_chain == 1 else 1

@@ -12,6 +12,11 @@ through ``from_torchfunc``, or traced with :func:`nutpie_amd.torch_trace.trace`)
 * :func:`regime_switching_model` — a Gaussian hidden Markov model (regime switching): the discrete state is summed out by the forward
   algorithm (``symbolic.hmm_marginal_lpdf``); ordered state means, one scale, a transition matrix of simplex rows.
   Vector: ``[mu_ordered__ (K), sigma_log__, P_0_simplex__ (K - 1), ..., P_{K-1}_simplex__ (K - 1)]``.
+* :func:`local_linear_trend_model` — a structural time series (level + slope, optionally one trigonometric seasonal harmonic) with the
+  state summed out by a Kalman filter (``symbolic.kalman_marginal_lpdf``); a share of the steps is missing.
+  Vector: ``[sigma_obs_log__, sigma_level_log__, sigma_slope_log__ (, sigma_seasonal_log__)]``.
+* :func:`ar_p_model` — AR(p) in companion form observed with noise: the transition matrix depends on the parameters.
+  Vector: ``[rho (p), sigma_log__, tau_log__]``.
 """
 
 from __future__ import annotations
@@ -275,3 +280,199 @@ def regime_switching_torch_density(T: int = 200, K: int = 2, seed: int = 2026101
         return lp + hmm_marginal(log_emission, torch.exp(log_rows)[:, None], initial).sum(-1)
 
     return K + 1 + K * (K - 1), logp
+
+
+# --------------------------------------------------------------------------- linear Gaussian state-space models (a Kalman filter)
+def _trend_matrices(seasonal_period):
+    """(transition, design row, init_cov diagonal) of level + slope (+ one harmonic of ``seasonal_period`` steps)"""
+    if seasonal_period is None:
+        return np.array([[1.0, 1.0], [0.0, 1.0]]), np.array([1.0, 0.0]), np.array([100.0, 1.0])
+    lam = 2.0 * math.pi / float(seasonal_period)
+    Tm = np.zeros((4, 4))
+    Tm[:2, :2] = [[1.0, 1.0], [0.0, 1.0]]
+    Tm[2:, 2:] = [[math.cos(lam), math.sin(lam)], [-math.sin(lam), math.cos(lam)]]
+    return Tm, np.array([1.0, 0.0, 1.0, 0.0]), np.array([100.0, 1.0, 25.0, 25.0])
+
+
+def synthetic_trend(T: int = 200, seasonal_period=None, R: int = 1, missing: float = 0.1, seed: int = 0):
+    """(y[R, T], observed[R, T]) drawn from the model itself: sigma_obs 0.5, sigma_level 0.3, sigma_slope 0.05, sigma_seasonal 0.1"""
+    rng = np.random.default_rng(20261020 + seed)
+    Tm, z, _ = _trend_matrices(seasonal_period)
+    scales = np.array([0.3, 0.05, 0.1, 0.1])[:z.size]
+    y = np.empty((R, T))
+    for r in range(R):
+        state = np.array([rng.normal(), 0.1 * rng.normal(), 2.0 * rng.normal(), 2.0 * rng.normal()])[:z.size]
+        for t in range(T):
+            y[r, t] = z @ state + 0.5 * rng.normal()
+            state = Tm @ state + scales * rng.normal(size=z.size)
+    observed = (rng.uniform(size=(R, T)) >= missing).astype(np.float64)
+    return y, observed
+
+
+def local_linear_trend_model(T: int = 200, seasonal_period=None, R: int = 1, missing: float = 0.1, seed: int = 0) -> S.Model:
+    """level_{t+1} = level_t + slope_t + sigma_level e, slope_{t+1} = slope_t + sigma_slope e (``seasonal_period``: plus one
+    trigonometric harmonic with disturbances sigma_seasonal; the state then has four elements), y_t = level_t (+ seasonal_t) +
+    sigma_obs e; every scale ~ HalfNormal(1); the state at t = 0 ~ N(0, diag(100, 1 (, 25, 25))); a share ``missing`` of the steps is
+    not observed.  The state is summed out: ``kalman_marginal_lpdf``.  ``R`` > 1: a panel of R series that share the parameters.
+    Deterministic ``filtered_level``: the filtered mean of the level at every step (``[R T]``)."""
+    y, observed = synthetic_trend(T, seasonal_period, R, missing, seed)
+    Tm, z, p0 = _trend_matrices(seasonal_period)
+    k = z.size
+    m = S.Model()
+    names = ["sigma_obs", "sigma_level", "sigma_slope"] + (["sigma_seasonal"] if k == 4 else [])
+    scales = [m.param(n, lower=0.0) for n in names]
+    for s_ in scales:
+        m.add_logp(S.halfnormal_lpdf(s_, 1.0))
+    m.dim("state", k)
+    if R == 1:
+        m.dim("time", T)
+        steps, along = "time", None
+    else:
+        m.dim("series", R)
+        m.dim("time", T)
+        steps, along = m.product("series", "time").name, "time"
+    kk = m.product("state", "state")
+    var = [scales[1] * scales[1], scales[2] * scales[2]] + ([scales[3] * scales[3]] * 2 if k == 4 else [])
+    Q = S.stack([var[i] if i == j else S.Expr.const(0.0) for i in range(k) for j in range(k)], kk)
+    args = dict(design=m.data("design", z, dim="state"), obs_var=scales[0] * scales[0], transition=m.data("transition", Tm.reshape(-1), dim=kk.name),
+                state_cov=Q, init_mean=m.data("init_mean", np.zeros(k), dim="state"), init_cov=m.data("init_cov", np.diag(p0).reshape(-1), dim=kk.name),
+                observed=m.data("observed", observed.reshape(-1), dim=steps), along=along)
+    obs = m.data("y", y.reshape(-1), dim=steps)
+    m.add_logp(S.kalman_marginal_lpdf(obs, **args))
+    m.deterministic("filtered_level", S.column(S.kalman_filtered_state(obs, **args), 0))
+    return m
+
+
+def _torch_filter(y, observed, Z, h, Tm, Q, a0, P0):
+    """the log-likelihood of [chains, R] series by a plain Kalman filter loop in matrix form (torch.autograd differentiates it):
+    y, observed [R, T]; Z [T, m] or [m]; h [chains]; Tm, Q, P0 [chains, m, m]; a0 [m]"""
+    import torch
+
+    C, (R, T) = h.shape[0], y.shape
+    a = a0.expand(C, R, -1)
+    P = P0[:, None].expand(C, R, -1, -1)
+    total = torch.zeros(C, R, dtype=h.dtype, device=h.device)
+    for t in range(T):
+        z = Z[t] if Z.dim() == 2 else Z
+        v = y[None, :, t] - a @ z
+        M = P @ z
+        F = h[:, None] + M @ z
+        seen = observed[None, :, t]
+        total = total - 0.5 * seen * (2.0 * _HALF_LOG_2PI + torch.log(F) + v * v / F)
+        K = seen[..., None] * M / F[..., None]
+        a = a + K * v[..., None]
+        P = P - K[..., :, None] * M[..., None, :]
+        a = a @ Tm.transpose(-1, -2)
+        P = Tm[:, None] @ P @ Tm.transpose(-1, -2)[:, None] + Q[:, None]
+    return total.sum(-1)
+
+
+def _halfnormal_log(ls):
+    """HalfNormal(1) of exp(ls) with the log transform's Jacobian"""
+    import torch
+
+    return 0.5 * math.log(2.0 / math.pi) - 0.5 * torch.exp(2.0 * ls) + ls
+
+
+def local_linear_trend_torch_density(T: int = 200, seasonal_period=None, R: int = 1, missing: float = 0.1, seed: int = 0, device="cpu"):
+    """The same log-density as :func:`local_linear_trend_model`, an independent implementation: a plain Python loop over the steps that
+    ``torch.autograd`` differentiates.  Returns ``(D, logp)``."""
+    import torch
+
+    y_np, obs_np = synthetic_trend(T, seasonal_period, R, missing, seed)
+    Tm_np, z_np, p0 = _trend_matrices(seasonal_period)
+    k = z_np.size
+    dev = torch.device(device) if isinstance(device, str) else torch.device("cuda", device)
+    y, observed, Tm, z = (torch.as_tensor(v, device=dev) for v in (y_np, obs_np, Tm_np, z_np))
+    P0 = torch.diag(torch.as_tensor(p0, device=dev))
+    a0 = torch.zeros(k, dtype=torch.float64, device=dev)
+
+    def logp(x):
+        var = torch.exp(2.0 * x)
+        diag = [var[:, 1], var[:, 2]] + ([var[:, 3], var[:, 3]] if k == 4 else [])
+        Q = torch.diag_embed(torch.stack(diag, dim=-1))
+        C = x.shape[0]
+        return _halfnormal_log(x).sum(-1) + _torch_filter(y, observed, z, var[:, 0], Tm[None].expand(C, k, k), Q, a0, P0[None].expand(C, k, k))
+
+    return 3 + (k == 4), logp
+
+
+def local_linear_trend_op_density(T: int = 200, seasonal_period=None, R: int = 1, missing: float = 0.1, seed: int = 0, device="cpu"):
+    """The same log-density with :func:`nutpie_amd.torch_trace.kalman_marginal`: what the tracer compiles onto the Kalman filter stage.
+    Returns ``(D, logp)``."""
+    import torch
+
+    from nutpie_amd.torch_trace import kalman_marginal
+
+    y_np, obs_np = synthetic_trend(T, seasonal_period, R, missing, seed)
+    Tm_np, z_np, p0 = _trend_matrices(seasonal_period)
+    k = z_np.size
+    dev = torch.device(device) if isinstance(device, str) else torch.device("cuda", device)
+    y, observed, Tm, z = (torch.as_tensor(v, device=dev) for v in (y_np, obs_np, Tm_np, z_np))
+    P0 = torch.diag(torch.as_tensor(p0, device=dev))
+    a0 = torch.zeros(k, dtype=torch.float64, device=dev)
+    eye = torch.eye(k, dtype=torch.float64, device=dev)
+
+    def logp(x):
+        var = torch.exp(2.0 * x)
+        diag = [var[:, 1], var[:, 2]] + ([var[:, 3], var[:, 3]] if k == 4 else [])
+        Q = torch.stack(diag, dim=-1)[:, :, None] * eye[None]
+        ll = kalman_marginal(y[None].expand(x.shape[0], R, T), z, var[:, 0, None, None], Tm, Q[:, None], a0, P0, observed[None])
+        return _halfnormal_log(x).sum(-1) + ll.sum(-1)
+
+    return 3 + (k == 4), logp
+
+
+def synthetic_ar(T: int = 200, p: int = 2, seed: int = 0) -> np.ndarray:
+    rng = np.random.default_rng(20261021 + seed)
+    phi = 0.6 / p * np.ones(p)
+    x = np.zeros(T + p)
+    for t in range(p, T + p):
+        x[t] = phi @ x[t - p:t][::-1] + 0.5 * rng.normal()
+    return x[p:] + 0.2 * rng.normal(size=T)
+
+
+def ar_p_model(T: int = 200, p: int = 2, seed: int = 0) -> S.Model:
+    """x_t = sum_i phi_i x_{t-i} + sigma e in companion form (the state holds the last p values), y_t = x_t + tau e;
+    phi_i = tanh(rho_i) / p (so that sum |phi_i| < 1: stationary), rho ~ Normal(0, 1), sigma, tau ~ HalfNormal(1); the state at t = 0
+    ~ N(0, 10 I).  The transition matrix depends on the parameters: the gradient reaches them through the filter's adjoint of it."""
+    y = synthetic_ar(T, p, seed)
+    m = S.Model()
+    m.dim("state", p)
+    m.dim("time", T)
+    rho = m.param("rho", dim="state")
+    sigma, tau = m.param("sigma", lower=0.0), m.param("tau", lower=0.0)
+    m.add_logp(S.normal_lpdf(rho, 0.0, 1.0).sum() + S.halfnormal_lpdf(sigma, 1.0) + S.halfnormal_lpdf(tau, 1.0))
+    kk = m.product("state", "state")
+    phi = S.tanh(rho) / float(p)
+    zero, one = S.Expr.const(0.0), S.Expr.const(1.0)
+    Tm = S.stack([S.elem(phi, j) if i == 0 else (one if j == i - 1 else zero) for i in range(p) for j in range(p)], kk)
+    Q = S.stack([sigma * sigma if i == j == 0 else zero for i in range(p) for j in range(p)], kk)
+    e0 = np.zeros(p)
+    e0[0] = 1.0
+    m.add_logp(S.kalman_marginal_lpdf(m.data("y", y, dim="time"), design=m.data("design", e0, dim="state"), obs_var=tau * tau, transition=Tm,
+                                      state_cov=Q, init_mean=0.0, init_cov=m.data("init_cov", (10.0 * np.eye(p)).reshape(-1), dim=kk.name)))
+    return m
+
+
+def ar_p_torch_density(T: int = 200, p: int = 2, seed: int = 0, device="cpu"):
+    """The same log-density as :func:`ar_p_model` by a plain Python loop with ``torch.autograd``.  Returns ``(D, logp)``."""
+    import torch
+
+    dev = torch.device(device) if isinstance(device, str) else torch.device("cuda", device)
+    y = torch.as_tensor(synthetic_ar(T, p, seed), device=dev)[None]
+    observed = torch.ones_like(y)
+    e0 = torch.zeros(p, dtype=torch.float64, device=dev)
+    e0[0] = 1.0
+    shift = torch.diag(torch.ones(p - 1, dtype=torch.float64, device=dev), -1)
+    P0 = 10.0 * torch.eye(p, dtype=torch.float64, device=dev)
+
+    def logp(x):
+        rho, ls, lt = x[:, :p], x[:, p], x[:, p + 1]
+        C = x.shape[0]
+        Tm = shift[None] + e0[None, :, None] * (torch.tanh(rho) / p)[:, None, :]
+        Q = torch.exp(2.0 * ls)[:, None, None] * (e0[:, None] * e0[None, :])[None]
+        lp = (-0.5 * rho * rho - _HALF_LOG_2PI).sum(-1) + _halfnormal_log(ls) + _halfnormal_log(lt)
+        return lp + _torch_filter(y, observed, e0, torch.exp(2.0 * lt), Tm, Q, torch.zeros_like(e0), P0[None].expand(C, p, p))
+
+    return p + 2, logp
