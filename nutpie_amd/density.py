@@ -50,6 +50,7 @@ import numpy as np
 
 from nutpie_amd import _lib
 from nutpie_amd.sample import CompiledModel
+from nutpie_amd.stage_families import chain_headers
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
@@ -191,16 +192,7 @@ def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verb
     nv = ((int(ndim) + 127) // 128 + waves - 1) // waves   # chunks of 128 dimensions per wave
     src = generated_source(user_source, layout)
     deps = [os.path.join(_CSRC, f) for f in ("kernels.hip", "engine_types.h", "kernel_families.h", "dense_tile.h")] + [os.path.join(_INCLUDE, "nphip_spec.h")]
-    if '#include "chain_linalg.h"' in user_source:
-        deps.append(os.path.join(_CSRC, "chain_linalg.h"))
-    if '#include "chain_scan.h"' in user_source:
-        deps.append(os.path.join(_CSRC, "chain_scan.h"))
-    if '#include "chain_matvec.h"' in user_source:
-        deps.append(os.path.join(_CSRC, "chain_matvec.h"))
-    if '#include "chain_hmm.h"' in user_source:
-        deps.append(os.path.join(_CSRC, "chain_hmm.h"))
-    if '#include "chain_kalman.h"' in user_source:
-        deps.extend(os.path.join(_CSRC, h) for h in ("chain_kalman.h", "chain_hmm.h"))     # (the Kalman header includes the HMM header's cross-lane moves)
+    deps += [os.path.join(_CSRC, f) for f in chain_headers(user_source)]     # (the stage families' headers the source includes)
     h = hashlib.sha256()
     h.update(src.encode())
     for d in deps:

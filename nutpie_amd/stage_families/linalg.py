@@ -1,0 +1,190 @@
+"""Matrix stages: one chain's dense matrices (``csrc/chain_linalg.h``).
+
+K x K (K <= 32) and K x N values, row-major on a fixed-size dimension (a ``Model.product``), that one device routine turns into another
+between two loops.  ``chol`` / ``trsv`` are the user's; the other three are the adjoints the gradient emits.  payload = (K, N): N the
+columns of the right-hand sides (K for the K x K stages)."""
+
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from nutpie_amd.expr import _HALF_LOG_2PI, Expr, _bcast, elem, log
+from nutpie_amd.stage_families import Family
+
+_MATOPS = ("chol", "trsv", "trsv_t", "trsv_gl", "chol_adj")
+MAX_MATRIX = 32     # the largest K a compiled density factors (8 KB per matrix and chain)
+
+
+def _side(e: Expr, what: str) -> int:
+    if e.dim is None or e.dim.size is None:
+        raise ValueError(f"{what}: a matrix lives on a fixed-size dimension (Model.product(rows, cols))")
+    k = int(round(math.sqrt(e.dim.size)))
+    if k * k != e.dim.size:
+        raise ValueError(f"{what}: a square matrix has K * K elements, dimension {e.dim.name!r} has {e.dim.size}")
+    return k
+
+
+def cholesky(A) -> Expr:
+    """``L`` with ``L L^T = A`` (K x K, row-major; the upper triangle of ``L`` is zero).  Only the lower triangle of ``A`` is read,
+    as by ``torch.linalg.cholesky``, and the gradient is that of what is read: an ``A`` filled below the diagonal only is as valid as a
+    symmetric one (for a symmetric ``A`` the parameter gradient is torch.autograd's).  A matrix that is not positive definite gives
+    NaN everywhere (the log-density is NaN there: an impossible point)."""
+    A = Expr.wrap(A)
+    k = _side(A, "cholesky")
+    return Expr("chol", (A,), A.dim, (k, k))
+
+
+def solve_lower(L, B) -> Expr:
+    """``L^-1 B`` for a lower-triangular K x K ``L`` (its upper triangle is not read) and a K x N ``B`` (row-major: element
+    (i, n) at ``i N + n``, every COLUMN a right-hand side — a value on ``Model.product(k, n)``).  The result lives where ``B`` does."""
+    L, B = Expr.wrap(L), Expr.wrap(B)
+    k = _side(L, "solve_lower")
+    if B.dim is None or B.dim.size is None or B.dim.size % k:
+        raise ValueError(f"solve_lower: the right-hand sides are a K x N value on a fixed-size dimension (K = {k})")
+    return Expr("trsv", (L, B), B.dim, (k, B.dim.size // k))
+
+
+def log_det_chol(L) -> Expr:
+    """``sum(log(diag(L)))``: half the log-determinant of ``L L^T``."""
+    k = _side(L, "log_det_chol")
+    total = None
+    for i in range(k):
+        t = log(elem(L, i * k + i))
+        total = t if total is None else total + t
+    return total
+
+
+def mvnormal_lpdf(value, mu, *, cov=None, chol=None) -> Expr:
+    """Sum over the N columns of the K x N ``value`` (element (i, n) at ``i N + n``: ``Model.product(k, n)``, every column one
+    draw) of the multivariate normal log-density with mean ``mu`` (a scalar or a value on the same dimension: ``Model.broadcast``)
+    and covariance ``cov`` (K x K) or its lower Cholesky factor ``chol``."""
+    if (cov is None) == (chol is None):
+        raise ValueError("mvnormal_lpdf: give cov= or chol=")
+    value, mu = Expr.wrap(value), Expr.wrap(mu)
+    L = cholesky(cov) if chol is None else Expr.wrap(chol)
+    k = _side(L, "mvnormal_lpdf")
+    if value.dim is None or value.dim.size is None or value.dim.size % k:
+        raise ValueError(f"mvnormal_lpdf: value is a K x N value on a fixed-size dimension (K = {k})")
+    n = value.dim.size // k
+    z = solve_lower(L, value - mu)
+    return -0.5 * (z * z).sum() - n * log_det_chol(L) - (n * k) * _HALF_LOG_2PI
+
+
+def _lkj_log_norm(eta: float, k: int) -> float:
+    """log of the LKJ(eta) normalising constant of K x K correlation matrices (Lewandowski, Kurowicka & Joe 2009, eq. 16)"""
+    c = 0.0
+    for i in range(1, k):
+        b = eta + (k - i - 1) / 2.0
+        c += (2.0 * eta - 2.0 + k - i) * (k - i) * math.log(2.0) + (k - i) * (2.0 * math.lgamma(b) - math.lgamma(2.0 * b))
+    return -c
+
+
+def lkj_corr_cholesky_lpdf(L, eta: float) -> Expr:
+    """Log-density of the Cholesky factor ``L`` (K x K) of an LKJ(``eta``) correlation matrix, with respect to its strictly lower
+    elements (Stan's ``lkj_corr_cholesky``): ``sum_{i >= 1} (K - i - 1 + 2 eta - 2) log L[i][i]`` + the normalising constant."""
+    L = Expr.wrap(L)
+    k = _side(L, "lkj_corr_cholesky_lpdf")
+    total = Expr.const(_lkj_log_norm(float(eta), k))
+    for i in range(1, k):
+        total = total + (k - i - 1 + 2.0 * float(eta) - 2.0) * log(elem(L, i * k + i))
+    return total
+
+
+# ---- host evaluation
+def _np_chol(a: np.ndarray) -> np.ndarray:
+    """[N, K, K] -> the lower Cholesky factors (lower triangles read; column by column as csrc/chain_linalg.h), NaN where a pivot fails"""
+    N, K, _ = a.shape
+    L = np.zeros_like(a)
+    bad = np.zeros(N, dtype=bool)
+    for j in range(K):
+        s = a[:, j:, j] - np.einsum("nik,nk->ni", L[:, j:, :j], L[:, j, :j])
+        d = s[:, 0]
+        ok = (d > 0.0) & np.isfinite(d)
+        bad |= ~ok
+        r = np.sqrt(np.where(ok, d, 1.0))
+        L[:, j, j] = r
+        L[:, j + 1:, j] = s[:, 1:] / r[:, None]
+    L[bad] = np.nan
+    return L
+
+
+def _np_solve_lower(L: np.ndarray, B: np.ndarray) -> np.ndarray:
+    """L^-1 B: L [N, K, K] (lower triangle read), B [N, K, M]"""
+    X = np.zeros(B.shape)
+    for i in range(L.shape[1]):
+        X[:, i] = (B[:, i] - np.einsum("nk,nkm->nm", L[:, i, :i], X[:, :i])) / L[:, i, i][:, None]
+    return X
+
+
+def _np_solve_lower_t(L: np.ndarray, G: np.ndarray) -> np.ndarray:
+    """L^-T G"""
+    Y = np.zeros(G.shape)
+    for i in reversed(range(L.shape[1])):
+        Y[:, i] = (G[:, i] - np.einsum("nk,nkm->nm", L[:, i + 1:, i], Y[:, i + 1:])) / L[:, i, i][:, None]
+    return Y
+
+
+def _np_matop(op: str, args: list[np.ndarray], k: int, m: int) -> np.ndarray:
+    N = args[0].shape[0]
+    mats = [v.reshape(N, k, -1) for v in args]
+    if op == "chol":
+        out = _np_chol(mats[0])
+    elif op == "trsv":
+        out = _np_solve_lower(mats[0], mats[1])
+    elif op == "trsv_t":
+        out = _np_solve_lower_t(mats[0], mats[1])
+    elif op == "trsv_gl":
+        out = -np.tril(np.einsum("nim,njm->nij", mats[0], mats[1]))
+    else:   # chol_adj: G = L^-T P L^-1, P = Phi(L^T tril(L-bar)) symmetrised (torch.autograd's G), folded onto the lower triangle
+        L, Lb = mats
+        M = np.tril(np.einsum("nki,nkj->nij", L, np.tril(Lb)))
+        P = 0.5 * (M + np.transpose(np.tril(M, -1), (0, 2, 1)))
+        Y = _np_solve_lower_t(L, P)
+        G = np.transpose(_np_solve_lower_t(L, np.transpose(Y, (0, 2, 1))), (0, 2, 1))
+        out = np.tril(G) + np.tril(np.transpose(G, (0, 2, 1)), -1)
+    return out.reshape(N, -1)
+
+
+def _numpy(n: Expr, args, data, N: int, dim_len) -> np.ndarray:
+    full = [np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, dim_len(x.dim))) for v, x in zip(args, n.args)]
+    return _np_matop(n.op, full, *n.payload)
+
+
+# ---- reverse mode
+def _chol_adjoint(n: Expr, g: Expr, ad):
+    a, = n.args
+    ad.acc(a, Expr("chol_adj", (n, _bcast(g, n.dim)), a.dim, n.payload))
+
+
+def _trsv_adjoint(n: Expr, g: Expr, ad):
+    a, b = n.args
+    gb = Expr("trsv_t", (a, _bcast(g, n.dim)), b.dim, n.payload)      # B-bar = L^-T X-bar
+    ad.acc(b, gb)
+    ad.acc(a, Expr("trsv_gl", (gb, n), a.dim, n.payload))            # L-bar = -tril(B-bar X^T)
+
+
+# ---- the generated call (every routine ends with the wave's barrier)
+def _call(gen, n: Expr) -> str:
+    k, m = n.payload
+    args = ", ".join(gen.store_name[a.id] for a in n.args)
+    out = gen.store_name[n.id]
+    fn = {"chol": f"cholesky<{k}>", "trsv": f"solve_lower<{k}, {m}>", "trsv_t": f"solve_lower_t<{k}, {m}, {m}, 1>",
+          "trsv_gl": f"solve_lower_adj_l<{k}, {m}>", "chol_adj": f"cholesky_adj<{k}>"}[n.op]
+    return f"    nphip_la::{fn}({args}, {out}, lane);"
+
+
+def _check(nodes, waves_per_chain):
+    # one wavefront per chain runs the matrix stages
+    k = max(n.payload[0] for n in nodes)
+    if k > MAX_MATRIX:
+        raise ValueError(f"a compiled density factors matrices of up to {MAX_MATRIX} x {MAX_MATRIX} (this model: {k} x {k})")
+    if waves_per_chain not in (None, 1):
+        raise ValueError("a model with matrix stages (cholesky / solve_lower) runs with waves_per_chain=1")
+    return 1
+
+
+FAMILY = Family(name="linalg", ops=_MATOPS, header="chain_linalg.h", call=_call, numpy=_numpy,
+                adjoint={"chol": _chol_adjoint, "trsv": _trsv_adjoint}, refusal="second derivatives of the matrix and scan stages",
+                check=_check, long_results=False)

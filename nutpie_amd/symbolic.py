@@ -70,6 +70,7 @@ from __future__ import annotations
 
 import math
 import os
+import types
 import weakref
 from typing import Any
 
@@ -89,874 +90,24 @@ _SEG_BATCH = os.environ.get("NUTPIE_AMD_SEG_MODE", "select") != "loop"   # (deve
 _UNROLL = 4   # iterations of a loop whose reads are issued together (a lone wave waits out every access otherwise)
 
 
-# --------------------------------------------------------------------------- IR
-class Dim:
-    """A named coordinate of the model: the range one wave-wide loop runs over."""
-
-    def __init__(self, name: str, size, runtime_len: str | None = None, runtime_div: int = 1, runtime_mul: int = 1):
-        self.name = name
-        self.size = size                  # int, or None for a data dimension whose length comes from the data block
-        self.runtime_len = runtime_len    # the data array whose length is the dimension's (times runtime_div: a matrix's rows)
-        self.runtime_div = runtime_div
-        self.runtime_mul = runtime_mul    # (the product of a data dimension with a fixed-size one: that many values per element)
-        self.factors: tuple[Dim, Dim] | None = None   # (rows, cols) of a Model.product
-        self._model = None                # (weak) the Model that declared it: where a scan's gradient registers its shifted read
-        self._scan_aux: dict[int, tuple] = {}   # row length T -> (index of element t - 1, "first element of a row" data or None)
-
-    def len_c(self) -> str:
-        if self.size is not None:
-            return str(self.size)
-        return f"data.n_{self.runtime_len}" + (f" / {self.runtime_div}" if self.runtime_div != 1 else "") + (f" * {self.runtime_mul}" if self.runtime_mul != 1 else "")
-
-    def len_py(self, data) -> int:
-        return self.size if self.size is not None else int(np.asarray(data[self.runtime_len]).size) // self.runtime_div * self.runtime_mul
-
-    def __repr__(self):
-        return f"Dim({self.name})"
-
-
-class Index:
-    """Integer data: for every element of ``dim`` the element of ``into`` it refers to."""
-
-    def __init__(self, name: str, dim: Dim, into: Dim):
-        self.name, self.dim, self.into = name, dim, into
-
-
-class Matrix:
-    """Float data with one row per element of ``dim`` and one column per element of ``cols`` (a design matrix).  ``X @ v`` with ``v``
-    on ``cols`` is the linear predictor on ``dim``.  With up to ``STAGE_ABOVE`` columns it is a sum over the columns of (column
-    x element of v), so that its transpose — the gradient with respect to ``v`` — is one wave-wide sum per column; with more (or
-    ``Model.matrix(..., stage=True)``) it is a stage between loops that one device routine runs (``csrc/chain_matvec.h``, DESIGN.md
-    §11.7), and ``X.T @ g`` with ``g`` on ``dim`` the transposed product."""
-
-    #: the automatic lowering keeps the sum over the columns up to this many columns: the stage from 64 on, the smallest measured
-    #: width where it samples faster (logistic regression, n = 2000, 512 chains: 1.46 against 0.91 M leapfrogs/s; at 32 columns 1.64
-    #: against 5.46 — profiles/matvec_wide_regression.txt)
-    STAGE_ABOVE = 63
-
-    def __init__(self, name: str, dim: Dim, cols: Dim, stage: bool | None = None, model=None):
-        self.name, self.dim, self.cols, self.stage = name, dim, cols, stage
-        self._model = model               # (weak) the Model that holds the data: a stage registers the transposed copy there
-
-    def column(self, c: int) -> "Expr":
-        return Expr("datacol", (), self.dim, (self.name, int(c), self.cols.size))
-
-    @property
-    def T(self) -> "_MatrixT":
-        """The transposed matrix: ``X.T @ g`` with ``g`` on the rows' dimension is a value on ``cols``."""
-        return _MatrixT(self)
-
-    def _staged_product(self) -> bool:
-        return self.stage if self.stage is not None else self.cols.size > Matrix.STAGE_ABOVE
-
-    def _register_stage(self):
-        m = self._model() if self._model is not None else None
-        if m is None:
-            raise ValueError(f"matrix {self.name!r} belongs to no Model")
-        m._matrix_stage(self)
-
-    def _rhs(self, v, outer: Dim, what: str) -> Dim | None:
-        """the dimension of the right-hand sides when ``v`` lives on a ``Model.product(outer, rhs)``, None when it lives on ``outer``"""
-        if isinstance(v, Expr) and v.dim is outer:
-            return None
-        if not isinstance(v, Expr) or v.dim is None or v.dim.factors is None or v.dim.factors[0] is not outer:
-            raise ValueError(f"matrix {self.name!r}{what} multiplies a vector on dimension {outer.name!r} (or a value on a product({outer.name!r}, right-hand sides))")
-        rhs = v.dim.factors[1]
-        if rhs.size > MAX_RHS:
-            raise ValueError(f"matrix {self.name!r}{what} multiplies up to {MAX_RHS} right-hand sides at once ({rhs.name!r} has {rhs.size})")
-        return rhs
-
-    def _product_dim(self, outer: Dim, rhs: Dim) -> Dim:
-        return self._model().product(outer.name, rhs.name)
-
-    def times(self, B: "Expr", out: Dim, R: int) -> "Expr":
-        """``X B`` for ``B`` on ANY fixed-size dimension of K x R elements (row-major), the n x R result on ``out`` (n x R elements) —
-        what a front end that keeps its tensors flat calls (the torch tracer); ``X @ B`` is this on a ``Model.product``."""
-        K = self.cols.size
-        if not isinstance(B, Expr) or B.dim is None or B.dim.size != K * R or not 1 <= R <= MAX_RHS or out.len_py(self._model()._data) != self.dim.len_py(self._model()._data) * R:
-            raise ValueError(f"matrix {self.name!r} times a K x R value: K = {K}, up to {MAX_RHS} right-hand sides, the result n x R")
-        self._register_stage()
-        return Expr("matvec", (B,), out, (self.name, K, int(R)))
-
-    def __matmul__(self, v) -> "Expr":
-        rhs = self._rhs(v, self.cols, "")
-        if rhs is not None:       # K x R coefficients: always the stage, the result n x R on product(rows, right-hand sides)
-            self._register_stage()
-            return Expr("matvec", (v,), self._product_dim(self.dim, rhs), (self.name, self.cols.size, rhs.size))
-        if self._staged_product():
-            self._register_stage()
-            return Expr("matvec", (v,), self.dim, (self.name, self.cols.size, 1))
-        total = None
-        for c in range(self.cols.size):
-            term = self.column(c) * elem(v, c)
-            total = term if total is None else total + term
-        return total
-
-
-class _MatrixT:
-    """``X.T``: what ``X.T @ g`` multiplies with (always the stage: the transposed product has no other form)."""
-
-    def __init__(self, matrix: Matrix):
-        self.matrix = matrix
-
-    def __matmul__(self, g) -> "Expr":
-        X = self.matrix
-        rhs = X._rhs(g, X.dim, " transposed")
-        X._register_stage()
-        if rhs is not None:
-            return Expr("matvec_t", (g,), X._product_dim(X.cols, rhs), (X.name, X.cols.size, rhs.size))
-        return Expr("matvec_t", (g,), X.cols, (X.name, X.cols.size, 1))
-
-
-class Expr:
-    """A node of the expression graph.  ``dim`` is None for scalars.  Nodes are hash-consed by ``Model``-independent structural
-    keys, so that the gradient graph shares its sub-expressions with the forward graph."""
-
-    _table: "weakref.WeakValueDictionary[tuple, Expr]" = None   # (weak: the nodes of a discarded model are collected with it)
-    _count = 0
-    __array_ufunc__ = None     # numpy scalars defer to the operators below
-
-    def __new__(cls, op: str, args: tuple = (), dim: Dim | None = None, payload: Any = None):
-        key = (op, tuple(id(a) for a in args), id(dim) if dim is not None else None, payload if not isinstance(payload, (Index, Dim)) else id(payload))
-        if Expr._table is None:
-            Expr._table = weakref.WeakValueDictionary()
-        hit = Expr._table.get(key)
-        if hit is not None:
-            return hit
-        self = object.__new__(cls)
-        self.op, self.args, self.dim, self.payload = op, tuple(args), dim, payload
-        self.id = Expr._count
-        Expr._count += 1
-        Expr._table[key] = self
-        return self
-
-    # ---- construction helpers
-    @staticmethod
-    def const(v) -> "Expr":
-        return Expr("const", (), None, float(v))
-
-    @staticmethod
-    def wrap(v) -> "Expr":
-        return v if isinstance(v, Expr) else Expr.const(v)
-
-    def is_const(self, v=None):
-        return self.op == "const" and (v is None or self.payload == v)
-
-    def _bin(self, op, other, swap=False):
-        a, b = Expr.wrap(self), Expr.wrap(other)
-        if swap:
-            a, b = b, a
-        return _binary(op, a, b)
-
-    __add__ = lambda s, o: s._bin("add", o)           # noqa: E731
-    __radd__ = lambda s, o: s._bin("add", o, True)    # noqa: E731
-    __sub__ = lambda s, o: s._bin("sub", o)           # noqa: E731
-    __rsub__ = lambda s, o: s._bin("sub", o, True)    # noqa: E731
-    __mul__ = lambda s, o: s._bin("mul", o)           # noqa: E731
-    __rmul__ = lambda s, o: s._bin("mul", o, True)    # noqa: E731
-    __truediv__ = lambda s, o: s._bin("div", o)       # noqa: E731
-    __rtruediv__ = lambda s, o: s._bin("div", o, True)  # noqa: E731
-
-    def __neg__(self):
-        return _unary("neg", self)
-
-    def __pow__(self, k):
-        if k == 2:
-            return self * self
-        raise TypeError("only `** 2` is supported: write other powers with exp / log")
-
-    def __getitem__(self, index: Index) -> "Expr":
-        if not isinstance(index, Index):
-            raise TypeError("an expression is indexed with a Model.index(...) array")
-        if self.dim is not index.into:
-            raise ValueError(f"index {index.name!r} points into dimension {index.into.name!r}, the expression lives on {self.dim.name if self.dim else 'no dimension'!r}")
-        return Expr("gather", (self,), index.dim, index)
-
-    def sum(self) -> "Expr":
-        if self.dim is None:
-            raise ValueError("sum() of a scalar")
-        return Expr("sum", (self,), None, None)
-
-    def max(self, constant: bool = False) -> "Expr":
-        """The largest element.  ``constant``: a value the result does not depend on in exact arithmetic (the shift of a softmax or a
-        log-sum-exp) — no gradient flows through it; otherwise the gradient goes to the element(s) that attain it."""
-        if self.dim is None:
-            return self
-        return Expr("max", (self,), None, "constant" if constant else None)
-
-    def __repr__(self):
-        return f"<{self.op}#{self.id}{'@' + self.dim.name if self.dim else ''}>"
-
-
-def _join(a: Expr, b: Expr) -> Dim | None:
-    if a.dim is None:
-        return b.dim
-    if b.dim is None or a.dim is b.dim:
-        return a.dim
-    raise ValueError(f"operands live on different dimensions ({a.dim.name!r}, {b.dim.name!r}): index one into the other")
-
-
-def _binary(op: str, a: Expr, b: Expr) -> Expr:
-    # constant folding and the identities the gradient graph is full of
-    if a.op == "const" and b.op == "const":
-        x, y = a.payload, b.payload
-        return Expr.const({"add": x + y, "sub": x - y, "mul": x * y, "div": x / y if y != 0.0 else math.copysign(math.inf, x)}[op])
-    if op == "mul" and b.op == "const" and a.op != "const":
-        a, b = b, a                                   # constants first
-    if op == "add":
-        if a.is_const(0.0):
-            return b
-        if b.is_const(0.0):
-            return a
-        if a.op == "rowpack" and b.op == "rowpack" and a.dim is b.dim:     # (the adjoints of the columns of one value, collected)
-            return Expr("rowpack", tuple(_binary("add", x, y) for x, y in zip(a.args, b.args)), a.dim, None)
-        if a is b:
-            return _binary("mul", Expr.const(2.0), a)
-    elif op == "sub":
-        if b.is_const(0.0):
-            return a
-        if a.is_const(0.0):
-            return _unary("neg", b)
-    elif op == "mul":
-        if a.is_const(1.0):
-            return b
-        if b.is_const(1.0):
-            return a
-        if a.is_const(0.0) or b.is_const(0.0):
-            return Expr.const(0.0)
-        if a.is_const(-1.0):
-            return _unary("neg", b)
-        if a.op == "const" and b.op == "mul" and b.args[0].op == "const":
-            return _binary("mul", Expr.const(a.payload * b.args[0].payload), b.args[1])     # c1 (c2 x) = (c1 c2) x
-        if a.op == "const" and b.op == "neg":
-            return _binary("mul", Expr.const(-a.payload), b.args[0])
-    elif op == "div":
-        if b.is_const(1.0):
-            return a
-        if a.is_const(0.0):
-            return a
-        if b.op == "const" and b.payload != 0.0:
-            return _binary("mul", a, Expr.const(1.0 / b.payload))     # (the numpy evaluation follows the same graph)
-        if a.dim is not None and b.dim is None:
-            # one division per evaluation instead of one per element
-            return _binary("mul", a, _binary("div", Expr.const(1.0), b))
-    return Expr(op, (a, b), _join(a, b))
-
-
-def _digamma_py(x: float) -> float:
-    """psi(x) the way the generated device code computes it (recurrence up to 10, then the asymptotic series)"""
-    if x <= 0.0:
-        if x == math.floor(x):
-            return math.nan
-        return _digamma_py(1.0 - x) - math.pi / math.tan(math.pi * x)
-    r = 0.0
-    while x < 10.0:
-        r -= 1.0 / x
-        x += 1.0
-    f = 1.0 / (x * x)
-    return r + math.log(x) - 0.5 / x - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760 - f / 12))))))
-
-
-_UNARY_FOLD = {"neg": lambda v: -v, "exp": math.exp, "log": math.log, "log1p": math.log1p, "sqrt": math.sqrt,
-               "softplus": lambda v: max(v, 0.0) + math.log1p(math.exp(-abs(v))), "sigmoid": lambda v: 1.0 / (1.0 + math.exp(-v)),
-               "tanh": math.tanh, "expm1": math.expm1, "erf": math.erf, "erfc": math.erfc, "sin": math.sin, "cos": math.cos, "atan": math.atan,
-               "lgamma": math.lgamma, "digamma": _digamma_py, "abs": abs, "sign": lambda v: float((v > 0) - (v < 0))}
-
-
-def _unary(op: str, a) -> Expr:
-    a = Expr.wrap(a)
-    if a.op == "const":
-        return Expr.const(_UNARY_FOLD[op](a.payload))
-    if op == "neg" and a.op == "neg":
-        return a.args[0]
-    if op == "neg" and a.op == "mul" and a.args[0].op == "const":
-        return _binary("mul", Expr.const(-a.args[0].payload), a.args[1])
-    if op == "log" and a.op == "exp":      # log sigma of a log-transformed sigma: the raw parameter
-        return a.args[0]
-    return Expr(op, (a,), a.dim)
-
-
-def exp(a):
-    return _unary("exp", a)
-
-
-def log(a):
-    return _unary("log", a)
-
-
-def log1p(a):
-    return _unary("log1p", a)
-
-
-def sqrt(a):
-    return _unary("sqrt", a)
-
-
-def softplus(a):
-    """log(1 + e^a), evaluated as max(a, 0) + log1p(e^-|a|)."""
-    return _unary("softplus", a)
-
-
-def sigmoid(a):
-    return _unary("sigmoid", a)
-
-
-def tanh(a):
-    return _unary("tanh", a)
-
-
-def expm1(a):
-    return _unary("expm1", a)
-
-
-def erf(a):
-    return _unary("erf", a)
-
-
-def erfc(a):
-    return _unary("erfc", a)
-
-
-def sin(a):
-    return _unary("sin", a)
-
-
-def cos(a):
-    return _unary("cos", a)
-
-
-def atan(a):
-    return _unary("atan", a)
-
-
-def lgamma(a):
-    return _unary("lgamma", a)
-
-
-def digamma(a):
-    return _unary("digamma", a)
-
-
-def absolute(a):
-    return _unary("abs", a)
-
-
-def sign(a):
-    return _unary("sign", a)
-
-
-def _join3(c: Expr, a: Expr, b: Expr) -> Dim | None:
-    d = None
-    for v in (c, a, b):
-        if v.dim is not None:
-            if d is not None and v.dim is not d:
-                raise ValueError(f"operands live on different dimensions ({d.name!r}, {v.dim.name!r})")
-            d = v.dim
-    return d
-
-
-def select(c, a, b, strict: bool = True) -> Expr:
-    """``a`` where ``c > 0`` (``strict``) resp. ``c >= 0``, else ``b`` — element-wise; the condition carries no gradient."""
-    c, a, b = Expr.wrap(c), Expr.wrap(a), Expr.wrap(b)
-    if c.op == "const":
-        return a if (c.payload > 0.0 if strict else c.payload >= 0.0) else b
-    if a is b:
-        return a
-    return Expr("sel_gt" if strict else "sel_ge", (c, a, b), _join3(c, a, b))
-
-
-def pad(v: Expr, dim: Dim) -> Expr:
-    """``v`` (on a shorter dimension of fixed size) on the first elements of ``dim``, zero on the rest."""
-    v = Expr.wrap(v)
-    if v.dim is None or v.dim is dim:
-        return v
-    if v.dim.size is None or dim.size is None or v.dim.size > dim.size:
-        raise ValueError("pad() goes from a fixed-size dimension to a longer fixed-size dimension")
-    return Expr("pad", (v,), dim, None)
-
-
-def trunc(v: Expr, dim: Dim) -> Expr:
-    """The first ``dim.size`` elements of ``v`` (on a longer dimension of fixed size), as a value on ``dim``."""
-    v = Expr.wrap(v)
-    if v.dim is None or v.dim is dim:
-        return v
-    if v.dim.size is None or dim.size is None or v.dim.size < dim.size:
-        raise ValueError("trunc() goes from a fixed-size dimension to a shorter fixed-size dimension")
-    if v.op == "pad" and v.args[0].dim is dim:
-        return v.args[0]
-    return Expr("trunc", (v,), dim, None)
-
-
-def where_lt(dim: Dim, k: int, a, b) -> Expr:
-    """``a`` on the first ``k`` elements of ``dim``, ``b`` on the rest."""
-    a, b = Expr.wrap(a), Expr.wrap(b)
-    for v in (a, b):
-        if v.dim is not None and v.dim is not dim:
-            raise ValueError("where_lt: operands must be scalars or live on `dim`")
-    return Expr("where_lt", (a, b), dim, int(k))
-
-
-def _bcast(a: Expr, dim: Dim) -> Expr:
-    return a if a.dim is dim else Expr("bcast", (a,), dim, None)
-
-
-def _dim_len(dim: Dim) -> Expr:
-    return Expr.const(dim.size) if dim.size is not None else Expr("dimlen", (), None, dim)
-
-
-def _segsum(e: Expr, index: Index) -> Expr:
-    if e.is_const(0.0):
-        return e
-    return Expr("segsum", (_bcast(e, index.dim),), index.into, index)
-
-
-def elem(v: Expr, c: int) -> Expr:
-    """Element ``c`` of a vector on a fixed-size dimension, as a scalar."""
-    if v.dim is None:
-        return v
-    if v.dim.size is None or not 0 <= c < v.dim.size:
-        raise ValueError("elem() needs a vector on a fixed-size dimension and an index inside it")
-    if v.op == "vparam" and c >= v.payload[1]:
-        return Expr.const(0.0)            # the padding element of a zero-sum parameter
-    if v.op == "stack":
-        return v.args[c]
-    if v.op == "bcast":
-        return v.args[0]
-    return Expr("elem", (v,), None, int(c))
-
-
-# --------------------------------------------------------------------------- one chain's dense matrices
-# Matrix stages: K x K (K <= 32) and K x N values, row-major on a fixed-size dimension (a ``Model.product``), that one device routine
-# (csrc/chain_linalg.h) turns into another between two loops.  ``chol`` / ``trsv`` are the user's; the other three are the adjoints
-# the gradient emits.  payload = (K, N): N the columns of the right-hand sides (K for the K x K stages).
-_MATOPS = ("chol", "trsv", "trsv_t", "trsv_gl", "chol_adj")
-MAX_MATRIX = 32     # the largest K a compiled density factors (8 KB per matrix and chain)
-
-
-def _side(e: Expr, what: str) -> int:
-    if e.dim is None or e.dim.size is None:
-        raise ValueError(f"{what}: a matrix lives on a fixed-size dimension (Model.product(rows, cols))")
-    k = int(round(math.sqrt(e.dim.size)))
-    if k * k != e.dim.size:
-        raise ValueError(f"{what}: a square matrix has K * K elements, dimension {e.dim.name!r} has {e.dim.size}")
-    return k
-
-
-def cholesky(A) -> Expr:
-    """``L`` with ``L L^T = A`` (K x K, row-major; the upper triangle of ``L`` is zero).  Only the lower triangle of ``A`` is read,
-    as by ``torch.linalg.cholesky``, and the gradient is that of what is read: an ``A`` filled below the diagonal only is as valid as a
-    symmetric one (for a symmetric ``A`` the parameter gradient is torch.autograd's).  A matrix that is not positive definite gives
-    NaN everywhere (the log-density is NaN there: an impossible point)."""
-    A = Expr.wrap(A)
-    k = _side(A, "cholesky")
-    return Expr("chol", (A,), A.dim, (k, k))
-
-
-def solve_lower(L, B) -> Expr:
-    """``L^-1 B`` for a lower-triangular K x K ``L`` (its upper triangle is not read) and a K x N ``B`` (row-major: element
-    (i, n) at ``i N + n``, every COLUMN a right-hand side — a value on ``Model.product(k, n)``).  The result lives where ``B`` does."""
-    L, B = Expr.wrap(L), Expr.wrap(B)
-    k = _side(L, "solve_lower")
-    if B.dim is None or B.dim.size is None or B.dim.size % k:
-        raise ValueError(f"solve_lower: the right-hand sides are a K x N value on a fixed-size dimension (K = {k})")
-    return Expr("trsv", (L, B), B.dim, (k, B.dim.size // k))
-
-
-def log_det_chol(L) -> Expr:
-    """``sum(log(diag(L)))``: half the log-determinant of ``L L^T``."""
-    k = _side(L, "log_det_chol")
-    total = None
-    for i in range(k):
-        t = log(elem(L, i * k + i))
-        total = t if total is None else total + t
-    return total
-
-
-def mvnormal_lpdf(value, mu, *, cov=None, chol=None) -> Expr:
-    """Sum over the N columns of the K x N ``value`` (element (i, n) at ``i N + n``: ``Model.product(k, n)``, every column one
-    draw) of the multivariate normal log-density with mean ``mu`` (a scalar or a value on the same dimension: ``Model.broadcast``)
-    and covariance ``cov`` (K x K) or its lower Cholesky factor ``chol``."""
-    if (cov is None) == (chol is None):
-        raise ValueError("mvnormal_lpdf: give cov= or chol=")
-    value, mu = Expr.wrap(value), Expr.wrap(mu)
-    L = cholesky(cov) if chol is None else Expr.wrap(chol)
-    k = _side(L, "mvnormal_lpdf")
-    if value.dim is None or value.dim.size is None or value.dim.size % k:
-        raise ValueError(f"mvnormal_lpdf: value is a K x N value on a fixed-size dimension (K = {k})")
-    n = value.dim.size // k
-    z = solve_lower(L, value - mu)
-    return -0.5 * (z * z).sum() - n * log_det_chol(L) - (n * k) * _HALF_LOG_2PI
-
-
-def _lkj_log_norm(eta: float, k: int) -> float:
-    """log of the LKJ(eta) normalising constant of K x K correlation matrices (Lewandowski, Kurowicka & Joe 2009, eq. 16)"""
-    c = 0.0
-    for i in range(1, k):
-        b = eta + (k - i - 1) / 2.0
-        c += (2.0 * eta - 2.0 + k - i) * (k - i) * math.log(2.0) + (k - i) * (2.0 * math.lgamma(b) - math.lgamma(2.0 * b))
-    return -c
-
-
-def lkj_corr_cholesky_lpdf(L, eta: float) -> Expr:
-    """Log-density of the Cholesky factor ``L`` (K x K) of an LKJ(``eta``) correlation matrix, with respect to its strictly lower
-    elements (Stan's ``lkj_corr_cholesky``): ``sum_{i >= 1} (K - i - 1 + 2 eta - 2) log L[i][i]`` + the normalising constant."""
-    L = Expr.wrap(L)
-    k = _side(L, "lkj_corr_cholesky_lpdf")
-    total = Expr.const(_lkj_log_norm(float(eta), k))
-    for i in range(1, k):
-        total = total + (k - i - 1 + 2.0 * float(eta) - 2.0) * log(elem(L, i * k + i))
-    return total
-
-
-# --------------------------------------------------------------------------- first-order linear recurrences
-# Scan stages: x_t = a_t x_{t-1} + b_t over R rows of T elements, row-major on a fixed-size dimension, that one device routine
-# (csrc/chain_scan.h) runs between two loops.  ``scan`` (args a, b, init) is the user's; ``rscan`` (args a, xbar) the adjoint the
-# gradient emits: lambda_t = a_{t+1} lambda_{t+1} + xbar_t, lambda_{T-1} = xbar_{T-1}.  ``a`` is a value on the dimension, a scalar, or
-# the constant 1 (a prefix sum); ``init`` a scalar or a value on the rows.  payload = (R, T).
-_SCANOPS = ("scan", "rscan")
-# Data-matrix stages: ``matvec`` E = X B (arg B on the matrix's columns, result on its rows) and ``matvec_t`` C = X^T G, each the
-# other's adjoint (csrc/chain_matvec.h).  payload = (name of the matrix, K columns, R right-hand sides).
-_MVOPS = ("matvec", "matvec_t")
-MAX_RHS = 16        # the right-hand sides of one product: that many accumulators per row block of a lane
-
-
-# A value on ``product(rows, rhs)`` (row-major, R = rhs.size values per row) and the R values on ``rows`` that are its columns:
-# ``column(E, r)`` reads column r (like a gather: from the stored array, in a loop over the rows), ``pack_columns([g_0 .. g_{R-1}],
-# dim)`` is the value whose columns the g_r are (stored by the loop over the rows that computes them) — each the other's adjoint.
-# What is element-wise ALONG the right-hand sides (a softmax over the classes) is written with these two, on the rows' loop.
-def column(E, r: int) -> Expr:
-    """Column ``r`` of a value on a ``Model.product(rows, rhs)``: a value on ``rows``."""
-    E = Expr.wrap(E)
-    if E.dim is None or E.dim.factors is None or not 0 <= int(r) < E.dim.factors[1].size:
-        raise ValueError("column(): a value on a Model.product(rows, rhs) and a column inside it")
-    if E.op == "rowpack":
-        return E.args[int(r)]
-    return Expr("rhscol", (E,), E.dim.factors[0], int(r))
-
-
-def pack_columns(columns, dim: Dim) -> Expr:
-    """The value on ``dim`` = ``Model.product(rows, rhs)`` whose columns are the given values on ``rows`` (or scalars)."""
-    columns = [Expr.wrap(c) for c in columns]
-    if dim.factors is None or len(columns) != dim.factors[1].size or any(c.dim is not None and c.dim is not dim.factors[0] for c in columns):
-        raise ValueError("pack_columns(): one value on the rows (or scalar) per column of a Model.product(rows, rhs)")
-    if all(c.is_const(0.0) for c in columns):
-        return Expr.const(0.0)
-    return Expr("rowpack", tuple(columns), dim, None)
-
-
-# HMM stages (csrc/chain_hmm.h): ``hmm_fwd`` (args logE, P, pi) is the scaled forward algorithm, ``hmm_bwd`` (args logE, P, the forward
-# result) the backward pass with the adjoints of P and pi — what the gradient emits.  A stage has ONE stored result, so each packs its
-# arrays on a dimension of its own: [alpha: R T K | c: R T | m: R T] resp. [beta: R T K | w: R T K | Pbar: K K | pibar: K]; ``hmm_part``
-# (payload: the offset) reads one of them as a value on the dimension it belongs to, ``hmm_ll`` the steps' log c_t + m_t — element-wise
-# reads of the stored array, like ``rhscol``.  payload = (R, T, K).
-_HMMOPS = ("hmm_fwd", "hmm_bwd")
-MAX_HMM_STATES = 16   # a lane keeps its column (row) of the transition matrix in registers, a group of up to 16 lanes owns a series
-# Kalman filter stages (csrc/chain_kalman.h): ``kalman_fwd`` (args y, Z, h, Tm, Q, a0, P0 [, obs]) is the filter, ``kalman_bwd`` (args y, Z,
-# h, Tm, Q, the forward result, vbar, Fbar [, obs]) its adjoint — what the gradient emits, with the adjoints of the stored v and F that
-# the IR's own loops compute as stored operands.  Each packs its arrays on a dimension of its own: [apred: R T m | Ppred: R T m m |
-# afilt: R T m | v: R T | F: R T] resp. [ybar: R T | hbar: R T | Zbar: R T m | Tbar: m m | Qbar: m m | a0bar: m | P0bar: m m |
-# per-series partials: R (3 m m + m)]; ``kalman_part`` (payload: the offset) reads one of them as a value on the dimension it belongs
-# to, like ``hmm_part``.  payload = (R, T, m, masked).
-_KALOPS = ("kalman_fwd", "kalman_bwd")
-MAX_KALMAN_STATE = 8   # a lane keeps its row of the state covariance in registers, a group of up to 8 lanes owns a series
-_STAGES = _MATOPS + _SCANOPS + _MVOPS + _HMMOPS + _KALOPS
-
-
-def _scan(a, b, init, R: int, T: int, rows: Dim | None = None) -> Expr:
-    a, b, init = Expr.wrap(a), Expr.wrap(b), Expr.wrap(init)
-    d = b.dim
-    if d is None or d.size is None or d.size != R * T:
-        raise ValueError("linear_recurrence: b is a value on a fixed-size dimension (R rows of T elements)")
-    if a.dim is not None and a.dim is not d:
-        raise ValueError("linear_recurrence: a is a scalar or a value on the dimension of b")
-    if init.dim is not None and (rows is None or init.dim is not rows):
-        raise ValueError("linear_recurrence: init is a scalar or a value on the rows of b")
-    if not (a.op == "const" and init.op == "const"):
-        # the gradient with respect to a or init reads x_{t-1}: a constant gather, registered with the model now
-        m = d._model() if d._model is not None else None
-        if m is None:
-            raise ValueError("linear_recurrence: b lives on a dimension of no Model")
-        m._scan_aux(d, R, T, rows if init.dim is not None else None)
-    return Expr("scan", (a, b, init), d, (int(R), int(T)))
-
-
-def linear_recurrence(a, b, init=0.0, along: str | None = None) -> Expr:
-    """``x_t = a_t x_{t-1} + b_t`` with ``x_{-1} = init``, along a dimension of fixed size.  ``b``: a value on it; ``a``: a scalar
-    expression or a value on the same dimension.  ``along``: the time axis of a ``Model.product(rows, time)`` — every row is its own
-    recurrence and ``init`` a scalar or a value on ``rows``; time must be the inner (second) axis.  Without ``along`` the whole
-    dimension is one series.  A non-finite ``a`` or ``b`` makes the values that depend on it non-finite; ``|a| > 1`` grows
-    geometrically and overflows on long series (not guarded)."""
-    b = Expr.wrap(b)
-    d = b.dim
-    if d is None or d.size is None:
-        raise ValueError("linear_recurrence: b is a value on a dimension of fixed size")
-    if along is None or (d.factors is None and along == d.name):
-        return _scan(a, b, init, 1, d.size)
-    if d.factors is None:
-        raise ValueError(f"linear_recurrence: along={along!r} names no axis of dimension {d.name!r}")
-    rows, time = d.factors
-    if along == rows.name and along != time.name:
-        raise ValueError(f"linear_recurrence: {along!r} is the outer axis of {d.name!r}; the time axis must be the inner (second) one")
-    if along != time.name:
-        raise ValueError(f"linear_recurrence: along={along!r} names no axis of dimension {d.name!r}")
-    return _scan(a, b, init, rows.size, time.size, rows)
-
-
-def cumsum(x, along: str | None = None) -> Expr:
-    """The prefix sum of ``x`` (``linear_recurrence(1.0, x, along=along)``)."""
-    return linear_recurrence(1.0, x, 0.0, along)
-
-
-def _scan_grads(n: Expr, lam: Expr) -> tuple[Expr | None, Expr | None]:
-    """adjoints of ``a`` and ``init`` in x = scan(a, b, init), lam the adjoint of b: a-bar_t = lam_t x_{t-1} (x_{-1} = init),
-    init-bar = a_0 lam_0 per row"""
-    a, _, init = n.args
-    R, T = n.payload
-    d = n.dim
-    if a.op == "const" and init.op == "const":
-        return None, None
-    prev, first, to_r = d._scan_aux[T]
-
-    def at_first(v, w):     # v on the first element of every row, w on the others
-        return where_lt(d, 1, v, w) if R == 1 else select(first, v, w)
-
-    ga = gi = None
-    if a.op != "const":
-        ga = lam * at_first(init if init.dim is None else init[to_r], n[prev])
-    if init.op != "const":
-        if R == 1 and init.dim is None:
-            gi = (a if a.dim is None else elem(a, 0)) * elem(lam, 0)
-        else:
-            first_terms = at_first(a * lam, 0.0)
-            gi = first_terms.sum() if init.dim is None else _segsum(first_terms, to_r)
-    return ga, gi
-
-# --------------------------------------------------------------------------- hidden Markov models
-def _hmm_model(d: Dim, what: str):
-    m = d._model() if d._model is not None else None
-    if m is None:
-        raise ValueError(f"{what}: log_emission lives on a dimension of no Model")
-    return m
-
-
-def _hmm_forward(logE, P, pi, R: int, T: int, K: int, steps: Dim, what: str = "hmm_marginal_lpdf") -> Expr:
-    """the forward stage for ``logE`` on ANY fixed-size dimension of R T K elements (row-major), ``steps`` a dimension of R T elements —
-    what a front end that keeps its tensors flat calls (the torch tracer); the public functions are this on a ``Model.product``"""
-    logE, P, pi = Expr.wrap(logE), Expr.wrap(P), Expr.wrap(pi)
-    d = logE.dim
-    if d is None or d.size is None or d.size != R * T * K or steps.size != R * T:
-        raise ValueError(f"{what}: log_emission is a value on a fixed-size dimension (R series of T steps of K states)")
-    if P.dim is None or P.dim.size != K * K:
-        raise ValueError(f"{what}: transition is a K x K value on a fixed-size dimension (K = {K}: the states of log_emission)")
-    if pi.dim is not None and pi.dim.size != K:
-        raise ValueError(f"{what}: initial is a scalar or a value on the {K} states of log_emission")
-    m = _hmm_model(d, what)
-    if pi.dim is None:
-        pi = _bcast(pi, m.dim(f"{d.name}__hmm_k", K))
-    packed = m.dim(f"{d.name}__hmm_f", R * T * K + 2 * R * T)
-    F = Expr("hmm_fwd", (logE, P, pi), packed, (int(R), int(T), int(K)))
-    packed._hmm_back = m.dim(f"{d.name}__hmm_b", 2 * R * T * K + K * K + K)      # (the backward stage's, should the gradient or a smoothed value need it)
-    return F
-
-
-def _hmm_backward(F: Expr) -> Expr:
-    logE, P, _ = F.args
-    return Expr("hmm_bwd", (logE, P, F), F.dim._hmm_back, F.payload)
-
-
-def _hmm_part(X: Expr, offset: int, dim: Dim) -> Expr:
-    return Expr("hmm_part", (X,), dim, int(offset))
-
-
-def _hmm_lpdf(F: Expr, steps: Dim) -> Expr:
-    """sum over the R T steps of log c_t + m_t: the IR's own reduction over ``steps``"""
-    return Expr("hmm_ll", (F,), steps, F.payload).sum()
-
-
-def _hmm_prob(F: Expr, smoothed: bool) -> Expr:
-    d = F.args[0].dim
-    alpha = _hmm_part(F, 0, d)
-    return alpha * _hmm_part(_hmm_backward(F), 0, d) if smoothed else alpha
-
-
-def _hmm_shape(log_emission, along, what: str):
-    logE = Expr.wrap(log_emission)
-    d = logE.dim
-    if d is None or d.size is None or d.factors is None:
-        raise ValueError(f"{what}: log_emission is a value on a Model.product(time, state) or product(product(series, time), state)")
-    steps, state = d.factors
-    if steps.size is None or state.size is None:
-        raise ValueError(f"{what}: log_emission is a value on a dimension of fixed size")
-    if along is None or (steps.factors is None and along == steps.name):
-        return logE, 1, steps.size, state.size, steps
-    if steps.factors is None:
-        raise ValueError(f"{what}: along={along!r} names no axis of dimension {steps.name!r}")
-    series, time = steps.factors
-    if along == series.name and along != time.name:
-        raise ValueError(f"{what}: {along!r} is the outer axis of {steps.name!r}; the time axis must be the inner (second) one")
-    if along != time.name:
-        raise ValueError(f"{what}: along={along!r} names no axis of dimension {steps.name!r}")
-    return logE, series.size, time.size, state.size, steps
-
-
-def hmm_marginal_lpdf(log_emission, transition, initial, along: str | None = None) -> Expr:
-    """The log-likelihood of a hidden Markov model with its discrete state summed out (Stan's ``hmm_marginal``): ``sum_r log(pi^T
-    diag(e_r0) P diag(e_r1) P ... diag(e_r,T-1) 1)`` with ``e = exp(log_emission)``, by the scaled forward algorithm.
-    ``log_emission``: the log density of observation t under state k, a value on ``Model.product(time, state)`` — one series — or on
-    ``product(product(series, time), state)`` with ``along`` naming the time axis: every series its own chain of states, the values
-    summed.  ``transition``: K x K on a fixed-size dimension (row-major; row i the weights of the next state given state i —
-    ``Model.transition_matrix``); ``initial``: a value on the K states, or one number for all.  The rows of ``transition`` and
-    ``initial`` need not sum to one: the value is the general product above, and so is the gradient with respect to every element.
-    K <= 16.  A ``log_emission`` of -inf is an impossible state; a step at which every state is impossible makes the density
-    non-finite (a divergence); a NaN makes what depends on it NaN (not guarded)."""
-    logE, R, T, K, steps = _hmm_shape(log_emission, along, "hmm_marginal_lpdf")
-    return _hmm_lpdf(_hmm_forward(logE, transition, initial, R, T, K, steps), steps)
-
-
-def hmm_state_prob(log_emission, transition, initial, along: str | None = None, smoothed: bool = True) -> Expr:
-    """The probability of every state at every step given the observations (Stan's ``hmm_hidden_state_prob``), a value on the
-    dimension of ``log_emission``: given all of the series' observations when ``smoothed`` (alpha_t beta_t of the forward-backward
-    algorithm — the gradient of :func:`hmm_marginal_lpdf` with respect to ``log_emission``), given those up to the step otherwise
-    (the filtered alpha_t).  Meant for ``Model.deterministic``: with the same arguments as the model's ``hmm_marginal_lpdf`` it reads
-    the arrays the density computes anyway.  It carries no gradient."""
-    logE, R, T, K, steps = _hmm_shape(log_emission, along, "hmm_state_prob")
-    return _hmm_prob(_hmm_forward(logE, transition, initial, R, T, K, steps, "hmm_state_prob"), bool(smoothed))
-
-
-# --------------------------------------------------------------------------- linear Gaussian state-space models
-def _kalman_sizes(R: int, T: int, m: int) -> tuple[int, int]:
-    return R * T * (2 * m + m * m + 2), R * T * (2 + m) + 3 * m * m + m + R * (3 * m * m + m)
-
-
-def _kalman_forward(y, Z, h, Tm, Q, a0, P0, obs, R: int, T: int, m: int, what: str = "kalman_marginal_lpdf") -> Expr:
-    """the filter stage for ``y`` on a dimension of R T elements, ``Z`` on one of R T m (row-major), ``h`` on that of ``y`` — what a front
-    end that keeps its tensors flat calls (the torch tracer); the public functions are this on the dimensions of a ``Model``"""
-    y, Z, h, Tm, Q, a0, P0 = (Expr.wrap(v) for v in (y, Z, h, Tm, Q, a0, P0))
-    steps = y.dim
-    if steps is None or steps.size is None or steps.size != R * T:
-        raise ValueError(f"{what}: y is a value or data on a fixed-size dimension (R series of T steps)")
-    if Z.dim is None or Z.dim.size != R * T * m:
-        raise ValueError(f"{what}: design is a value on the {m} states or on product(steps, state)")
-    for name, v in (("transition", Tm), ("state_cov", Q), ("init_cov", P0)):
-        if v.dim is None or v.dim.size != m * m:
-            raise ValueError(f"{what}: {name} is an m x m value on a fixed-size dimension (m = {m}: the states of design)")
-    if a0.dim is None or a0.dim.size != m:
-        raise ValueError(f"{what}: init_mean is a scalar or a value on the {m} states")
-    if h.dim is not steps:
-        raise ValueError(f"{what}: obs_var is a scalar or a value on the dimension of y")
-    if obs is not None and (obs.op != "data" or obs.dim is not steps):
-        raise ValueError(f"{what}: observed is data (0 or 1) on the dimension of y")
-    model = steps._model() if steps._model is not None else None
-    if model is None:
-        raise ValueError(f"{what}: y lives on a dimension of no Model")
-    n_f, n_b = _kalman_sizes(R, T, m)
-    # (a second filter over the same steps with another split into series or another state: dimensions named after its shape)
-    tag = "" if model._dims.get(f"{steps.name}__kf_f", Dim("", n_f)).size == n_f and model._dims.get(f"{steps.name}__kf_b", Dim("", n_b)).size == n_b \
-        else f"_{R}x{T}x{m}"
-    packed = model.dim(f"{steps.name}__kf_f{tag}", n_f)
-    packed._kalman_back = model.dim(f"{steps.name}__kf_b{tag}", n_b)
-    args = (y, Z, h, Tm, Q, a0, P0) + ((obs,) if obs is not None else ())
-    return Expr("kalman_fwd", args, packed, (int(R), int(T), int(m), obs is not None))
-
-
-def _kalman_backward(F: Expr, vbar: Expr, Fbar: Expr) -> Expr:
-    y, Z, h, Tm, Q = F.args[:5]
-    return Expr("kalman_bwd", (y, Z, h, Tm, Q, F, vbar, Fbar) + F.args[7:], F.dim._kalman_back, F.payload)
-
-
-def _kalman_part(X: Expr, offset: int, dim: Dim) -> Expr:
-    return Expr("kalman_part", (X,), dim, int(offset))
-
-
-def _kalman_terms(F: Expr) -> Expr:
-    """the steps' -1/2 obs (log 2 pi + log F + v^2 / F): element-wise IR on the stored v and F"""
-    R, T, m, masked = F.payload
-    steps = F.args[0].dim
-    o = R * T * (2 * m + m * m)
-    v, Fv = _kalman_part(F, o, steps), _kalman_part(F, o + R * T, steps)
-    terms = (2.0 * _HALF_LOG_2PI) + log(Fv) + v * v / Fv
-    if masked:
-        terms = F.args[7] * terms
-    return -0.5 * terms
-
-
-def _kalman_args(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed, along, what: str):
-    y, Z, h, a0 = Expr.wrap(y), Expr.wrap(design), Expr.wrap(obs_var), Expr.wrap(init_mean)
-    steps = y.dim
-    if steps is None or steps.size is None:
-        raise ValueError(f"{what}: y is a value or data on a fixed-size dimension (steps, or product(series, steps))")
-    if along is None or (steps.factors is None and along == steps.name):
-        R, T = 1, steps.size
-    elif steps.factors is None:
-        raise ValueError(f"{what}: along={along!r} names no axis of dimension {steps.name!r}")
-    else:
-        series, time = steps.factors
-        if along == series.name and along != time.name:
-            raise ValueError(f"{what}: {along!r} is the outer axis of {steps.name!r}; the time axis must be the inner (second) one")
-        if along != time.name:
-            raise ValueError(f"{what}: along={along!r} names no axis of dimension {steps.name!r}")
-        R, T = series.size, time.size
-    model = steps._model() if steps._model is not None else None
-    if model is None or Z.dim is None or Z.dim.size is None:
-        raise ValueError(f"{what}: design is a value on the states or on product(steps, state), y lives on a dimension of a Model")
-    if Z.dim.factors is not None and Z.dim.factors[0] is steps:
-        state = Z.dim.factors[1]
-    elif Z.dim.factors is None:
-        state = Z.dim
-        Z = model.broadcast(Z, steps.name, state.name)
-    else:
-        raise ValueError(f"{what}: design is a value on the states or on product({steps.name!r}, state)")
-    if state.size is None:
-        raise ValueError(f"{what}: the state dimension has a fixed size")
-    if h.dim is None:
-        h = _bcast(h, steps)
-    if a0.dim is None:
-        a0 = _bcast(a0, state)
-    obs = None if observed is None else Expr.wrap(observed)
-    return y, Z, h, transition, state_cov, a0, init_cov, obs, R, T, state.size, state
-
-
-def kalman_marginal_lpdf(y, *, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None, along: str | None = None) -> Expr:
-    """The log-likelihood of a linear Gaussian state-space model with its state summed out by a Kalman filter:
-    ``state_0 ~ N(init_mean, init_cov)`` (before the first observation), ``y_t ~ N(design_t . state_t, obs_var_t)``,
-    ``state_{t+1} ~ N(transition state_t, state_cov)``; the value is ``-1/2 sum observed (log 2 pi + log F_t + v_t^2 / F_t)`` with the
-    innovations v and their variances F.  ``y``: a value or data on ``steps`` — one series — or on ``product(series, steps)`` with
-    ``along`` naming the inner (time) axis: every series its own filter with the same parameters, the values summed; an observation
-    offset is ``y - d``.  ``design``: a value on ``product(y.dim, state)`` or on ``state`` alone (the same row at every step);
-    ``obs_var``: a scalar or a value on ``y.dim``; ``transition``, ``state_cov``, ``init_cov``: m x m on fixed-size dimensions
-    (row-major); ``init_mean``: a scalar or a value on ``state``.  ``observed``: data on ``y.dim``, 0 where the observation is
-    missing (the step then only predicts).  m <= 8.  The covariances are used as given (not symmetrised), and the gradient is that of
-    what is evaluated.  A step with F <= 0 or a non-finite input makes the density NaN (a divergence; not guarded)."""
-    *args, R, T, m, _ = _kalman_args(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed, along, "kalman_marginal_lpdf")
-    return _kalman_terms(_kalman_forward(*args, R, T, m)).sum()
-
-
-def kalman_filtered_state(y, *, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None, along: str | None = None,
-                          predicted: bool = False) -> Expr:
-    """The mean of the state at every step given the observations up to and including the step (``predicted``: up to the step before),
-    a value on ``product(y.dim, state)``.  Meant for ``Model.deterministic``: with the same arguments as the model's
-    ``kalman_marginal_lpdf`` it reads the arrays the density computes anyway.  It carries no gradient."""
-    *args, R, T, m, state = _kalman_args(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed, along, "kalman_filtered_state")
-    F = _kalman_forward(*args, R, T, m, what="kalman_filtered_state")
-    steps = F.args[0].dim
-    out = steps._model().product(steps.name, state.name)
-    return _kalman_part(F, 0 if predicted else R * T * (m + m * m), out)
-
-
-def stack(scalars, dim: Dim) -> Expr:
-    """The vector on ``dim`` whose elements are the given scalars."""
-    scalars = [Expr.wrap(v) for v in scalars]
-    if dim.size is None or len(scalars) != dim.size or any(v.dim is not None for v in scalars):
-        raise ValueError("stack() needs one scalar per element of a fixed-size dimension")
-    if all(v.is_const(0.0) for v in scalars):
-        return Expr.const(0.0)
-    return Expr("stack", tuple(scalars), dim, None)
+# The IR — dimensions, nodes, the element-wise functions — is nutpie_amd/expr.py; the stages between loops (matrix, scan, data-matrix product,
+# HMM, Kalman filter: builders, adjoint rules, host evaluation, the generated calls) are one module each under nutpie_amd/stage_families/.
+# Callers import this module and no other: it re-exports their names, the private ones other modules and the tests use included.
+from nutpie_amd.expr import (_HALF_LOG_2PI, _UNARY_FOLD, Dim, Expr, Index, _bcast, _binary, _digamma_py, _dim_len, _join, _join3,  # noqa: F401
+                             _segsum, _topo, _unary, absolute, atan, cos, digamma, elem, erf, erfc, exp, expm1, lgamma, log, log1p, pad,
+                             select, sigmoid, sign, sin, softplus, sqrt, stack, tanh, trunc, where_lt)
+from nutpie_amd.stage_families import _READERS, _STAGES, FAMILIES, family_of
+from nutpie_amd.stage_families.hmm import (MAX_HMM_STATES, _HMMOPS, _hmm_backward, _hmm_forward, _hmm_lpdf, _hmm_model, _hmm_part, _hmm_prob,  # noqa: F401
+                                           _hmm_shape, _np_hmm, hmm_marginal_lpdf, hmm_state_prob)
+from nutpie_amd.stage_families.kalman import (MAX_KALMAN_STATE, _KALOPS, _kalman_args, _kalman_backward, _kalman_forward, _kalman_part,  # noqa: F401
+                                              _kalman_sizes, _kalman_terms, _np_kalman, kalman_filtered_state, kalman_marginal_lpdf)
+from nutpie_amd.stage_families.linalg import (MAX_MATRIX, _MATOPS, _lkj_log_norm, _np_chol, _np_matop, _np_solve_lower, _np_solve_lower_t, _side,  # noqa: F401
+                                              cholesky, lkj_corr_cholesky_lpdf, log_det_chol, mvnormal_lpdf, solve_lower)
+from nutpie_amd.stage_families.matvec import MAX_RHS, _MVOPS, Matrix, _MatrixT, column, pack_columns  # noqa: F401
+from nutpie_amd.stage_families.scan import _SCANOPS, _np_scan, _scan, _scan_grads, cumsum, linear_recurrence  # noqa: F401
 
 
 # --------------------------------------------------------------------------- densities
-_HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
-
-
 def normal_lpdf(x, mu, sigma) -> Expr:
     x, mu, sigma = Expr.wrap(x), Expr.wrap(mu), Expr.wrap(sigma)
     z = (x - mu) / sigma
@@ -1121,24 +272,6 @@ def poisson_log_lpmf(y, eta, log_factorial) -> Expr:
 _TWO_OVER_SQRT_PI = 2.0 / math.sqrt(math.pi)
 
 
-def _topo(roots) -> list[Expr]:
-    seen, order = set(), []
-    stack = [(r, False) for r in roots]
-    while stack:
-        n, done = stack.pop()
-        if done:
-            order.append(n)
-            continue
-        if n.id in seen:
-            continue
-        seen.add(n.id)
-        stack.append((n, True))
-        for a in n.args:
-            if a.id not in seen:
-                stack.append((a, False))
-    return order
-
-
 def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
     """d out / d wrt[k] as expressions (``out`` a scalar; every ``wrt[k]`` a parameter node).  The adjoint of a node lives on the
     node's dimension; a scalar-valued adjoint of a dimensioned node means the same value for every element."""
@@ -1161,16 +294,11 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
         adj[target.id] = adj[target.id] + e if target.id in adj else e
 
     elem_adj: dict[int, dict[int, Expr]] = {}     # vector -> {element: adjoint of elem(vector, element)}
-    kal_adj: dict[int, dict[str, Expr]] = {}      # Kalman filter stage -> the adjoints of its stored v and F
+    stage_adj: dict[int, dict] = {}               # stage -> what the rules of its readers left for the family's ``finish``
+    ad = types.SimpleNamespace(acc=acc, reduce_to=reduce_to, pending=lambda stage: stage_adj.setdefault(stage.id, {}))   # what a family's rule is given
     for n in reversed(order):
-        if n.id in kal_adj:       # every consumer of the filter has been visited: its adjoint is one backward stage
-            parts = kal_adj.pop(n.id)
-            R, T, m, _ = n.payload
-            y, Z, h, Tm, Q, a0, P0 = n.args[:7]
-            back = _kalman_backward(n, *(_bcast(parts.get(k, Expr.const(0.0)), y.dim) for k in ("v", "F")))
-            for target, off in ((y, 0), (h, R * T), (Z, 2 * R * T), (Tm, R * T * (2 + m)), (Q, R * T * (2 + m) + m * m),
-                                (a0, R * T * (2 + m) + 2 * m * m), (P0, R * T * (2 + m) + 2 * m * m + m)):
-                acc(target, _kalman_part(back, off, target.dim))
+        if n.id in stage_adj:     # every consumer of the stage has been visited: the family turns what they left into the stage's adjoint
+            family_of(n.op).finish(n, stage_adj.pop(n.id), ad)
             continue
         if n.id in elem_adj:      # every consumer of n has been visited: the adjoints of its extracted elements as one vector
             parts = elem_adj.pop(n.id)
@@ -1259,50 +387,14 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
             acc(a, _segsum(g, n.payload))
         elif n.op == "segsum":
             acc(a, _bcast(g, n.payload.into)[n.payload])
-        elif n.op == "chol":
-            acc(a, Expr("chol_adj", (n, _bcast(g, d)), a.dim, n.payload))
-        elif n.op == "trsv":
-            gb = Expr("trsv_t", (a, _bcast(g, d)), b.dim, n.payload)      # B-bar = L^-T X-bar
-            acc(b, gb)
-            acc(a, Expr("trsv_gl", (gb, n), a.dim, n.payload))            # L-bar = -tril(B-bar X^T)
-        elif n.op == "scan":
-            lam = Expr("rscan", (a, _bcast(g, d)), d, n.payload)          # the adjoint recurrence, run backwards
-            acc(b, lam)
-            ga, gi = _scan_grads(n, lam)
-            if ga is not None:
-                acc(a, reduce_to(ga, d, a))
-            if gi is not None:
-                acc(n.args[2], gi)
         elif n.op == "rhscol":
             zero = Expr.const(0.0)
             acc(a, pack_columns([_bcast(g, d) if c == n.payload else zero for c in range(a.dim.factors[1].size)], a.dim))
-        elif n.op == "matvec":
-            acc(a, Expr("matvec_t", (_bcast(g, d),), a.dim, n.payload))   # B-bar = X^T E-bar
-        elif n.op == "matvec_t":
-            acc(a, Expr("matvec", (_bcast(g, d),), a.dim, n.payload))     # G-bar = X C-bar
-        elif n.op == "hmm_ll":
-            if g.dim is not None and g.op == "gather" and g.args[0].op == "bcast":
-                g = g.args[0].args[0]      # (per-series values summed by the caller, as the torch op returns them: one scalar for every step)
-            if g.dim is not None:
-                raise NotImplementedError("the steps of an HMM likelihood carry one weight: their sum is what is differentiated")
-            logE, P, pi = a.args
-            R, T, K = n.payload
-            back = _hmm_backward(a)
-            acc(logE, g * (_hmm_part(a, 0, logE.dim) * _hmm_part(back, 0, logE.dim)))      # alpha_t beta_t
-            acc(P, g * _hmm_part(back, 2 * R * T * K, P.dim))
-            acc(pi, g * _hmm_part(back, 2 * R * T * K + K * K, pi.dim))
-        elif n.op == "kalman_part" and a.op == "kalman_fwd" and n.payload >= a.payload[0] * a.payload[1] * (2 * a.payload[2] + a.payload[2] ** 2):
-            R, T, m, _ = a.payload
-            which = "v" if n.payload == R * T * (2 * m + m * m) else "F"
-            slot = kal_adj.setdefault(a.id, {})
-            g = _bcast(g, d)
-            slot[which] = slot[which] + g if which in slot else g
-        elif n.op == "kalman_part" or n.op in _KALOPS:
-            raise NotImplementedError("second derivatives of the Kalman filter stages (kalman_filtered_state carries no gradient)")
-        elif n.op == "hmm_part" or n.op in _HMMOPS:
-            raise NotImplementedError("second derivatives of the HMM stages (hmm_state_prob carries no gradient)")
-        elif n.op in _STAGES:
-            raise NotImplementedError("second derivatives of the matrix and scan stages")
+        elif family_of(n.op) is not None:     # a stage or a reader of one: the family's rule
+            fam = family_of(n.op)
+            rule = fam.adjoint.get(n.op)
+            if rule is None or rule(n, g, ad) is False:
+                raise NotImplementedError(fam.refusal)
         else:
             raise AssertionError(n.op)
     return [adj.get(w.id, Expr.const(0.0)) for w in wrt]
@@ -1318,173 +410,6 @@ def _np_unary(op: str, a: np.ndarray) -> np.ndarray:
 
         return {"erf": sp.erf, "erfc": sp.erfc, "lgamma": sp.gammaln, "digamma": sp.digamma}[op](a)
     return {"tanh": np.tanh, "expm1": np.expm1, "sin": np.sin, "cos": np.cos, "atan": np.arctan, "abs": np.abs, "sign": np.sign}[op](a)
-
-
-def _np_chol(a: np.ndarray) -> np.ndarray:
-    """[N, K, K] -> the lower Cholesky factors (lower triangles read; column by column as csrc/chain_linalg.h), NaN where a pivot fails"""
-    N, K, _ = a.shape
-    L = np.zeros_like(a)
-    bad = np.zeros(N, dtype=bool)
-    for j in range(K):
-        s = a[:, j:, j] - np.einsum("nik,nk->ni", L[:, j:, :j], L[:, j, :j])
-        d = s[:, 0]
-        ok = (d > 0.0) & np.isfinite(d)
-        bad |= ~ok
-        r = np.sqrt(np.where(ok, d, 1.0))
-        L[:, j, j] = r
-        L[:, j + 1:, j] = s[:, 1:] / r[:, None]
-    L[bad] = np.nan
-    return L
-
-
-def _np_solve_lower(L: np.ndarray, B: np.ndarray) -> np.ndarray:
-    """L^-1 B: L [N, K, K] (lower triangle read), B [N, K, M]"""
-    X = np.zeros(B.shape)
-    for i in range(L.shape[1]):
-        X[:, i] = (B[:, i] - np.einsum("nk,nkm->nm", L[:, i, :i], X[:, :i])) / L[:, i, i][:, None]
-    return X
-
-
-def _np_solve_lower_t(L: np.ndarray, G: np.ndarray) -> np.ndarray:
-    """L^-T G"""
-    Y = np.zeros(G.shape)
-    for i in reversed(range(L.shape[1])):
-        Y[:, i] = (G[:, i] - np.einsum("nk,nkm->nm", L[:, i + 1:, i], Y[:, i + 1:])) / L[:, i, i][:, None]
-    return Y
-
-
-def _np_matop(op: str, args: list[np.ndarray], k: int, m: int) -> np.ndarray:
-    N = args[0].shape[0]
-    mats = [v.reshape(N, k, -1) for v in args]
-    if op == "chol":
-        out = _np_chol(mats[0])
-    elif op == "trsv":
-        out = _np_solve_lower(mats[0], mats[1])
-    elif op == "trsv_t":
-        out = _np_solve_lower_t(mats[0], mats[1])
-    elif op == "trsv_gl":
-        out = -np.tril(np.einsum("nim,njm->nij", mats[0], mats[1]))
-    else:   # chol_adj: G = L^-T P L^-1, P = Phi(L^T tril(L-bar)) symmetrised (torch.autograd's G), folded onto the lower triangle
-        L, Lb = mats
-        M = np.tril(np.einsum("nki,nkj->nij", L, np.tril(Lb)))
-        P = 0.5 * (M + np.transpose(np.tril(M, -1), (0, 2, 1)))
-        Y = _np_solve_lower_t(L, P)
-        G = np.transpose(_np_solve_lower_t(L, np.transpose(Y, (0, 2, 1))), (0, 2, 1))
-        out = np.tril(G) + np.tril(np.transpose(G, (0, 2, 1)), -1)
-    return out.reshape(N, -1)
-
-
-def _np_scan(op: str, args: list[np.ndarray], R: int, T: int, N: int) -> np.ndarray:
-    """the recurrence (``scan``) or its adjoint (``rscan``) by a plain loop over time: the checker (the bitwise reference of the device routine is the CPU oracle's ``oracle_chain_scan``)"""
-    def rows(v):
-        return np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, R * T)).reshape(N, R, T)
-
-    a, b = rows(args[0]), rows(args[1])
-    out = np.empty((N, R, T))
-    if op == "scan":
-        prev = np.broadcast_to(args[2][:, None] if args[2].ndim == 1 else args[2], (N, R))
-        for t in range(T):
-            prev = a[:, :, t] * prev + b[:, :, t]
-            out[:, :, t] = prev
-    else:
-        lam = b[:, :, T - 1]
-        out[:, :, T - 1] = lam
-        for t in range(T - 2, -1, -1):
-            lam = a[:, :, t + 1] * lam + b[:, :, t]
-            out[:, :, t] = lam
-    return out.reshape(N, R * T)
-
-
-def _np_hmm(op: str, args: list[np.ndarray], R: int, T: int, K: int, N: int) -> np.ndarray:
-    """the packed result of the forward (``hmm_fwd``) or backward (``hmm_bwd``) stage by the plain scaled algorithm: the checker (the
-    bitwise reference of the device routines is tests/fixtures/hmm_reference.c)"""
-    def full(v, n):
-        return np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, n))
-
-    logE, P = full(args[0], R * T * K).reshape(N, R, T, K), full(args[1], K * K).reshape(N, K, K)
-    if op == "hmm_fwd":
-        pi = full(args[2], K)
-        alpha, c = np.empty((N, R, T, K)), np.empty((N, R, T))
-        m = logE.max(axis=3)
-        e = np.exp(logE - m[..., None])
-        for t in range(T):
-            a = (pi[:, None, :] if t == 0 else np.einsum("nri,nij->nrj", alpha[:, :, t - 1], P)) * e[:, :, t]
-            c[:, :, t] = a.sum(axis=2)
-            alpha[:, :, t] = a / c[:, :, t, None]
-        return np.concatenate([alpha.reshape(N, -1), c.reshape(N, -1), m.reshape(N, -1)], axis=1)
-    F = args[2]
-    alpha, c, m = F[:, :R * T * K].reshape(N, R, T, K), F[:, R * T * K:R * T * K + R * T].reshape(N, R, T), F[:, R * T * K + R * T:].reshape(N, R, T)
-    e = np.exp(logE - m[..., None])
-    beta, w = np.ones((N, R, T, K)), np.empty((N, R, T, K))
-    for t in range(T - 1, -1, -1):
-        w[:, :, t] = e[:, :, t] * beta[:, :, t] / c[:, :, t, None]
-        if t:
-            beta[:, :, t - 1] = np.einsum("nij,nrj->nri", P, w[:, :, t])
-    Pbar = np.einsum("nrti,nrtj->nij", alpha[:, :, :-1], w[:, :, 1:])
-    return np.concatenate([beta.reshape(N, -1), w.reshape(N, -1), Pbar.reshape(N, -1), w[:, :, 0].sum(axis=1)], axis=1)
-
-
-def _np_kalman(op: str, args: list[np.ndarray], R: int, T: int, m: int, masked: bool, N: int) -> np.ndarray:
-    """the packed result of the filter (``kalman_fwd``) or its adjoint (``kalman_bwd``) by the plain sequential algorithm in matrix form,
-    in the precision of its arguments: the checker (the bitwise reference of the device routines is tests/fixtures/kalman_reference.c)"""
-    dt = np.result_type(*args)
-
-    def full(v, *shape):
-        v = np.asarray(v)
-        return np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, int(np.prod(shape)))).reshape(N, *shape)
-
-    y, Z, h, Tm, Q = full(args[0], R, T), full(args[1], R, T, m), full(args[2], R, T), full(args[3], m, m), full(args[4], m, m)
-    fwd = op == "kalman_fwd"
-    obs = full(args[7 if fwd else 8], R, T) != 0 if masked else np.ones((N, R, T), bool)
-    if fwd:
-        a = np.broadcast_to(full(args[5], m)[:, None], (N, R, m)).astype(dt)
-        P = np.broadcast_to(full(args[6], m, m)[:, None], (N, R, m, m)).astype(dt)
-        apred, Ppred, afilt = np.empty((N, R, T, m), dt), np.empty((N, R, T, m, m), dt), np.empty((N, R, T, m), dt)
-        vs, Fs = np.empty((N, R, T), dt), np.empty((N, R, T), dt)
-        for t in range(T):
-            z, seen = Z[:, :, t], obs[:, :, t]
-            apred[:, :, t], Ppred[:, :, t] = a, P
-            M = np.einsum("nrij,nrj->nri", P, z)
-            v = np.where(seen, y[:, :, t] - np.einsum("nrk,nrk->nr", z, a), 0.0)
-            Fv = np.where(seen, h[:, :, t] + np.einsum("nrk,nrk->nr", z, M), 1.0)
-            K = np.where(seen[..., None], M / Fv[..., None], 0.0)
-            af = a + K * v[..., None]
-            Pf = P - K[..., :, None] * M[..., None, :]
-            vs[:, :, t], Fs[:, :, t], afilt[:, :, t] = v, Fv, af
-            a = np.einsum("nik,nrk->nri", Tm, af)
-            P = Q[:, None] + np.einsum("nik,nrkl,njl->nrij", Tm, Pf, Tm)
-        return np.concatenate([v_.reshape(N, -1) for v_ in (apred, Ppred, afilt, vs, Fs)], axis=1)
-    F = np.asarray(args[5])
-    cuts = np.cumsum([R * T * m, R * T * m * m, R * T * m, R * T])
-    apred, Ppred, _, vs, Fs = (v_.reshape(N, R, T, *sh) for v_, sh in zip(np.split(F, cuts, axis=1), ((m,), (m, m), (m,), (), ())))
-    vbar, Fbar = full(args[6], R, T), full(args[7], R, T)
-    ybar, hbar, Zbar = np.zeros((N, R, T), dt), np.zeros((N, R, T), dt), np.zeros((N, R, T, m), dt)
-    Tb, Qb = np.zeros((N, R, m, m), dt), np.zeros((N, R, m, m), dt)
-    ab, Pb = np.zeros((N, R, m), dt), np.zeros((N, R, m, m), dt)
-    for t in range(T - 1, -1, -1):
-        z, seen, a, P, v, Fv = Z[:, :, t], obs[:, :, t], apred[:, :, t], Ppred[:, :, t], vs[:, :, t], Fs[:, :, t]
-        M = np.einsum("nrij,nrj->nri", P, z)
-        K = np.where(seen[..., None], M / Fv[..., None], 0.0)
-        af = a + K * v[..., None]
-        Pf = P - K[..., :, None] * M[..., None, :]
-        if t < T - 1:
-            Qb = Qb + Pb
-            Tb = Tb + np.einsum("nrij,njl,nrkl->nrik", Pb, Tm, Pf) + np.einsum("nrji,njl,nrlk->nrik", Pb, Tm, Pf) + ab[..., :, None] * af[..., None, :]
-            Pfb = np.einsum("nli,nrlj,njk->nrik", Tm, Pb, Tm)
-            afb = np.einsum("nik,nri->nrk", Tm, ab)
-        else:
-            Pfb, afb = np.zeros_like(Pb), np.zeros_like(ab)
-        Kb = afb * v[..., None] - np.einsum("nrij,nrj->nri", Pfb, M)
-        vb = vbar[:, :, t] + np.einsum("nri,nri->nr", afb, K)
-        Fb = Fbar[:, :, t] - np.einsum("nri,nri->nr", Kb, K) / Fv
-        Mb = -np.einsum("nrij,nri->nrj", Pfb, K) + Kb / Fv[..., None] + Fb[..., None] * z
-        s3, s4 = seen[..., None], seen[..., None, None]
-        ybar[:, :, t], hbar[:, :, t] = np.where(seen, vb, 0.0), np.where(seen, Fb, 0.0)
-        Zbar[:, :, t] = np.where(s3, Fb[..., None] * M + np.einsum("nrik,nri->nrk", P, Mb) - vb[..., None] * a, 0.0)
-        ab = np.where(s3, afb - vb[..., None] * z, afb)
-        Pb = np.where(s4, Pfb + Mb[..., :, None] * z[..., None, :], Pfb)
-    parts = np.concatenate([Tb.reshape(N, R, -1), Qb.reshape(N, R, -1), ab, Pb.reshape(N, R, -1)], axis=2)
-    return np.concatenate([ybar.reshape(N, -1), hbar.reshape(N, -1), Zbar.reshape(N, -1), parts.sum(axis=1), parts.reshape(N, -1)], axis=1)
 
 
 def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.ndarray]:
@@ -1575,34 +500,14 @@ def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.
                 idx = np.asarray(data[n.payload.name], dtype=np.int64)
                 v = np.zeros((N, dim_len(n.dim)))
                 np.add.at(v, (slice(None), idx), a)
-            elif n.op in _MATOPS:
-                args = [np.broadcast_to(val[x_.id][:, None] if val[x_.id].ndim == 1 else val[x_.id], (N, dim_len(x_.dim))) for x_ in n.args]
-                v = _np_matop(n.op, args, *n.payload)
-            elif n.op in _SCANOPS:
-                v = _np_scan(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
-            elif n.op in _HMMOPS:
-                v = _np_hmm(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
-            elif n.op in _KALOPS:
-                v = _np_kalman(n.op, [val[x_.id] for x_ in n.args], *n.payload, N)
-            elif n.op in ("hmm_part", "kalman_part"):
-                v = a[:, n.payload:n.payload + dim_len(n.dim)]
-            elif n.op == "hmm_ll":
-                R, T, K = n.payload
-                v = np.log(a[:, R * T * K:R * T * K + R * T]) + a[:, R * T * K + R * T:]
+            elif family_of(n.op) is not None:
+                v = family_of(n.op).numpy(n, [val[x_.id] for x_ in n.args], data, N, dim_len)
             elif n.op == "rhscol":
                 R = n.args[0].dim.factors[1].size
                 v = np.broadcast_to(a[:, None] if a.ndim == 1 else a, (N, dim_len(n.args[0].dim))).reshape(N, -1, R)[:, :, n.payload]
             elif n.op == "rowpack":
                 rows = dim_len(n.dim.factors[0])
                 v = np.stack([np.broadcast_to(val[x_.id][:, None] if val[x_.id].ndim == 1 else val[x_.id], (N, rows)) for x_ in n.args], axis=2).reshape(N, -1)
-            elif n.op in _MVOPS:
-                name, K, R = n.payload
-                X = np.asarray(data[name], dtype=np.float64).reshape(-1, K)
-                arg = np.broadcast_to(a[:, None] if a.ndim == 1 else a, (N, dim_len(n.args[0].dim)))
-                if n.op == "matvec":      # [N, K, R] -> [N, n, R]
-                    v = np.einsum("ik,nkr->nir", X, arg.reshape(N, K, R)).reshape(N, -1)
-                else:                     # [N, n, R] -> [N, K, R]
-                    v = np.einsum("ik,nir->nkr", X, arg.reshape(N, -1, R)).reshape(N, -1)
             else:
                 raise AssertionError(n.op)
         val[n.id] = np.asarray(v, dtype=np.float64)
@@ -1611,17 +516,14 @@ def evaluate(nodes: list[Expr], x: np.ndarray, data: dict[str, Any]) -> list[np.
 
 # --------------------------------------------------------------------------- code generation
 def _series_lengths(nodes) -> set[int]:
-    """the lengths of the dimensions the series of the forward-backward stages among ``nodes`` live on: steps x states, steps, time
-    (by length, not by name: a traced model has its own dimension per tensor)"""
+    """the lengths of the dimensions the series of the stages among ``nodes`` live on (``Family.series_lengths``: steps x states, steps,
+    time — by length, not by name: a traced model has its own dimension per tensor)"""
     sizes: set[int] = set()
     for n in nodes:
-        if n.op in _HMMOPS:
-            R, T, K = n.payload[:3]
-            sizes |= {R * T * K, R * T, T}
-        elif n.op in _KALOPS:
-            R, T, m = n.payload[:3]
-            sizes |= {R * T * m, R * T, T}
+        if n.op in _STAGES:
+            sizes |= family_of(n.op).series_lengths(n.payload)
     return sizes
+
 
 
 class _Out:
@@ -1664,7 +566,7 @@ class _Gen:
         # _UNROLL times whatever that length, as loops over a data dimension are: the length of a series then changes constants of the
         # source and nothing else.  The loop bounds are constants, so the compiler drops the iterations a short series never reaches.
         # Other loops, and so other models, keep their source byte for byte.
-        self.even_unroll: set[int] = set(getattr(model, "_hmm_lengths", ())) | _series_lengths(self.order)
+        self.even_unroll: set[int] = set(getattr(model, "_stage_series_lengths", ())) | _series_lengths(self.order)
         self.level: dict[int, int] = {}
         for n in self.order:
             lv = max([self.level[a.id] for a in n.args], default=0)
@@ -1714,7 +616,7 @@ class _Gen:
                 if n.op == "segsum":
                     evaluated.setdefault(n.id, set()).add(lv[1])
                     continue               # (its argument was stored by an earlier loop)
-                if n.op in ("gather", "pad", "trunc", "rhscol", "hmm_part", "hmm_ll", "kalman_part"):
+                if n.op in ("gather", "pad", "trunc", "rhscol") + _READERS:
                     continue
                 stack.extend(n.args)
         for nid, levels in evaluated.items():
@@ -1735,7 +637,7 @@ class _Gen:
                 seen.add(n.id)
                 if n.op == "vparam":
                     reads.setdefault(n.id, set()).add(key)
-                if n.op in ("stack", "gather", "segsum", "pad", "trunc", "rhscol", "rowpack", "hmm_part", "hmm_ll", "kalman_part") + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
+                if n.op in ("stack", "gather", "segsum", "pad", "trunc", "rhscol", "rowpack") + _READERS + _STAGES or (n.id in self.stored and self.level[n.id] < key[1]):
                     continue
                 stack.extend(n.args)
         for nid, loops in reads.items():
@@ -1783,16 +685,9 @@ class _Gen:
             emit(stage_src)
         if any(n.op == "digamma" for n in self.order):
             emit(_DIGAMMA_SOURCE)
-        if any(n.op in _MATOPS for n in self.order):
-            emit('#include "chain_linalg.h"')
-        if any(n.op in _SCANOPS for n in self.order):
-            emit('#include "chain_scan.h"')
-        if any(n.op in _MVOPS for n in self.order):
-            emit('#include "chain_matvec.h"')
-        if any(n.op in _HMMOPS for n in self.order):
-            emit('#include "chain_hmm.h"')
-        if any(n.op in _KALOPS for n in self.order):
-            emit('#include "chain_kalman.h"')
+        for fam in FAMILIES:
+            if any(n.op in fam.ops for n in self.order):
+                emit(f'#include "{fam.header}"')
         emit(f"__device__ double {self.fn_name}(const NphipData& data, int dim, const double* x, double* g, double* lds, const double* shared, int lane) {{")
         # dimension lengths, data pointers (shared LDS where staged, else global), LDS scratch
         for d in m._dims.values():
@@ -1867,11 +762,11 @@ class _Gen:
                 emit("    nphip_chain_barrier();")
             for n in self.order:
                 if n.op in _STAGES and self.level[n.id] == lv:
-                    emit(self.matop_call(n) if n.op in _MATOPS else self.scan_call(n) if n.op in _SCANOPS else self.hmm_call(n) if n.op in _HMMOPS else self.kalman_call(n) if n.op in _KALOPS else self.mv_call(n))
-                    if n.op in _KALOPS:
-                        mark(f"stage {n.op}<{', '.join(str(int(v)) for v in n.payload)}>")
-                    if n.op in _MVOPS:
-                        mark(f"stage {n.op}<{n.payload[1]}, {n.payload[2]}> of {n.payload[0]}")
+                    fam = family_of(n.op)
+                    emit(fam.call(self, n))
+                    label = fam.section(n)
+                    if label is not None:
+                        mark(label)
             mark(f"scalars of level {lv}")
             # loops of this level, one per dimension that has something to produce here
             for d in m._dims.values():
@@ -1911,68 +806,6 @@ class _Gen:
             emit(f"    return {self.sref(self.logp)};")
         emit("}")
         return "\n".join(L), shared_fields
-
-    # ---- matrix stages (csrc/chain_linalg.h; every routine ends with the wave's barrier)
-    def matop_call(self, n: Expr) -> str:
-        k, m = n.payload
-        args = ", ".join(self.store_name[a.id] for a in n.args)
-        out = self.store_name[n.id]
-        fn = {"chol": f"cholesky<{k}>", "trsv": f"solve_lower<{k}, {m}>", "trsv_t": f"solve_lower_t<{k}, {m}, {m}, 1>",
-              "trsv_gl": f"solve_lower_adj_l<{k}, {m}>", "chol_adj": f"cholesky_adj<{k}>"}[n.op]
-        return f"    nphip_la::{fn}({args}, {out}, lane);"
-
-    # ---- scan stages (csrc/chain_scan.h; the routine ends with the chain's barrier)
-    def scan_call(self, n: Expr) -> str:
-        R, T = n.payload
-        a, v = n.args[0], n.args[1]
-        init = n.args[2] if n.op == "scan" else Expr.const(0.0)
-        kind = "A_ONE" if a.is_const(1.0) else ("A_SCALAR" if a.dim is None else "A_ARRAY")
-        none = "(const double*)nullptr"
-        coef = self.store_name[a.id] if a.dim is not None else none
-        a_s = self.sref(a) if a.dim is None else "1.0"
-        irow = init.dim is not None
-        i_arr = self.store_name[init.id] if irow else none
-        i_s = "0.0" if irow else self.sref(init)
-        rev = "true" if n.op == "rscan" else "false"
-        return (f"    nphip_scan::linear_recurrence<{R}, {T}, nphip_scan::{kind}, {rev}, {'true' if irow else 'false'}>"
-                f"({coef}, {a_s}, {self.store_name[v.id]}, {i_arr}, {i_s}, {self.store_name[n.id]}, lane);")
-
-    # ---- data-matrix stages (csrc/chain_matvec.h; the routine ends with the chain's barrier)
-    def mv_call(self, n: Expr) -> str:
-        name, K, R = n.payload
-        arg, out = self.store_name[n.args[0].id], self.store_name[n.id]
-        rows = self.m._matrix_t[name].dim          # (the length the routines take is the matrix's rows, whatever R)
-        # the routines read the matrix from device memory — also a matrix that the loops of a sum over its columns read from the
-        # workgroup's staged copy in LDS (a narrow matrix with `X @ beta` unrolled and `X.T @ g` beside it)
-        if n.op == "matvec":
-            return f"    nphip_mv::times<{K}, {R}>(data.{name}__t, {arg}, {out}, n_{rows.name}, lane);"
-        return f"    nphip_mv::times_t<{K}, {R}>(data.{name}, {arg}, {out}, n_{rows.name}, lane);"
-
-    # ---- HMM stages (csrc/chain_hmm.h; every routine ends with the chain's barrier)
-    def hmm_call(self, n: Expr) -> str:
-        R, T, K = n.payload
-        args = ", ".join(self.store_name[a.id] for a in n.args)
-        out = self.store_name[n.id]
-        if n.op == "hmm_fwd":
-            return f"    nphip_hmm::forward<{R}, {T}, {K}>({args}, {out}, lane);"
-        call = f"    nphip_hmm::backward<{R}, {T}, {K}>({args}, {out}, lane);"
-        if any(m.op == "hmm_part" and m.args[0] is n and m.payload >= 2 * R * T * K for m in self.order):
-            # (the adjoints of P and pi: the density's gradient reads them, the smoothed probabilities of the expand function do not)
-            call += f" nphip_hmm::transition_adjoint<{R}, {T}, {K}>({self.store_name[n.args[2].id]}, {out}, lane);"
-        return call
-
-    # ---- Kalman filter stages (csrc/chain_kalman.h; every routine ends with the chain's barrier)
-    def kalman_call(self, n: Expr) -> str:
-        R, T, m, masked = n.payload
-        name = lambda a: self.store_name[a.id]      # noqa: E731
-        obs = name(n.args[-1]) if masked else "(const double*)nullptr"
-        shape = f"{R}, {T}, {m}, {'true' if masked else 'false'}"
-        if n.op == "kalman_fwd":
-            y, Z, h, Tm, Q, a0, P0 = n.args[:7]
-            return f"    nphip_kalman::forward<{shape}>({name(y)}, {obs}, {name(Z)}, {name(h)}, {name(Tm)}, {name(Q)}, {name(a0)}, {name(P0)}, {name(n)}, lane);"
-        y, Z, h, Tm, Q, F, vbar, Fbar = n.args[:8]
-        return (f"    nphip_kalman::backward<{shape}>({name(y)}, {obs}, {name(Z)}, {name(h)}, {name(Tm)}, {name(Q)}, {name(F)}, {name(vbar)}, {name(Fbar)}, "
-                f"{name(n)}, lane);")
 
     # ---- scalars
     def sref(self, n: Expr) -> str:
@@ -2047,13 +880,10 @@ class _Gen:
                 elif n.op == "rhscol":
                     src = n.args[0]
                     stages[0].append(f"        const double {name} = {self.store_name[src.id]}[j_{u} * {src.dim.factors[1].size} + {n.payload}];")
-                elif n.op in ("hmm_part", "kalman_part"):
-                    stages[0].append(f"        const double {name} = {self.store_name[n.args[0].id]}[{n.payload} + j_{u}];")
-                elif n.op == "hmm_ll":
-                    R_, T_, K_ = n.payload
-                    arr = self.store_name[n.args[0].id]
-                    stages[0].append(f"        const double {name}_c = {arr}[{R_ * T_ * K_} + j_{u}], {name}_m = {arr}[{R_ * T_ * K_ + R_ * T_} + j_{u}];")
-                    stages[3].append(f"        const double {name} = log({name}_c) + {name}_m;")
+                elif n.op in _READERS:
+                    loads, arithmetic = family_of(n.op).read(n, name, self.store_name[n.args[0].id], f"j_{u}")
+                    stages[0].extend(loads)
+                    stages[3].extend(arithmetic)
                 elif n.op == "gather":
                     src, index = n.args[0], n.payload
                     iname = f"k{index.name}_{u}"
@@ -2868,22 +1698,12 @@ class Model:
             self._det = [(n, e) for n, e in self._det if n in wanted or n in free]
         logp = self.logp_expr()
         grads = gradient(logp, self._params)
-        mats = [n for n in _topo([logp] + grads + [e for _, e in self._det]) if n.op in _MATOPS]
-        if mats:
-            # one wavefront per chain runs the matrix stages (csrc/chain_linalg.h)
-            k = max(n.payload[0] for n in mats)
-            if k > MAX_MATRIX:
-                raise ValueError(f"a compiled density factors matrices of up to {MAX_MATRIX} x {MAX_MATRIX} (this model: {k} x {k})")
-            if waves_per_chain not in (None, 1):
-                raise ValueError("a model with matrix stages (cholesky / solve_lower) runs with waves_per_chain=1")
-            waves_per_chain = 1
-        hmms = [n for n in _topo([logp] + grads + [e for _, e in self._det]) if n.op in _HMMOPS]
-        if hmms and max(n.payload[2] for n in hmms) > MAX_HMM_STATES:
-            raise ValueError(f"a compiled density sums out up to {MAX_HMM_STATES} hidden states (this model: {max(n.payload[2] for n in hmms)})")
-        kals = [n for n in _topo([logp] + grads + [e for _, e in self._det]) if n.op in _KALOPS]
-        if kals and max(n.payload[2] for n in kals) > MAX_KALMAN_STATE:
-            raise ValueError(f"a compiled density filters states of up to {MAX_KALMAN_STATE} dimensions (this model: {max(n.payload[2] for n in kals)})")
-        self._hmm_lengths = _series_lengths(hmms + kals)   # (the expand function's loops follow the same rule, whatever it reports)
+        stages = [n for n in _topo([logp] + grads + [e for _, e in self._det]) if n.op in _STAGES]
+        for fam in FAMILIES:      # every family's limits on its stages, and the waves per chain it runs with
+            mine = [n for n in stages if n.op in fam.ops]
+            if mine:
+                waves_per_chain = fam.check(mine, waves_per_chain)
+        self._stage_series_lengths = _series_lengths(stages)   # (the expand function's loops follow the same rule, whatever it reports)
         self._plan_staging([logp] + grads + [e for _, e in self._det])
         if waves_per_chain is None:
             for waves_per_chain in (1, 2, 4):
@@ -3013,7 +1833,7 @@ class Model:
         else:
             out_names, out_shapes = names, shapes
         egen = _Gen(self, Expr.const(0.0), [], waves_per_chain, outputs=offs, fn_name="nphip_expand") if (fixed and det) else None
-        if egen is not None and any(n.op in _SCANOPS + _MVOPS + _HMMOPS + _KALOPS for n in egen.order):
+        if egen is not None and any(n.op in _STAGES and family_of(n.op).long_results for n in egen.order):
             # (the generated expand keeps its arrays in LDS, (4 rows per workgroup with one wave per row) + the staged data: a long scan
             #  that does not fit is expanded on the host)
             rows_per_block = 4 if waves_per_chain == 1 else 1
