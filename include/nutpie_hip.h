@@ -205,7 +205,8 @@ typedef struct {
                                  * way a failed roll call does.  The dense-precision Gaussian (nphip_model_dense_gaussian): 0 = its resident
                                  * form when the job fills the die-local clusters of workgroups that share a round's GEMM (otherwise a launch
                                  * per evaluation is faster: DESIGN.md section 12), 1 = a launch per evaluation, N > 1 = the resident form */
-    int32_t reserved_;
+    int32_t no_leaf_pairs;      /* 1: the one-wave register-resident kernels take every tree leaf by itself, never the two leaves of a
+                                 * level-0 pair in one trip (A/B measurements, tests; results do not depend on it) */
 } nphip_launch_t;
 
 void nphip_launch_defaults(nphip_launch_t*);

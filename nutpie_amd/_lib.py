@@ -67,7 +67,7 @@ class _Launch(C.Structure):
         ("graph_steps", C.c_int32),
         ("host_groups", C.c_int32),
         ("host_persist", C.c_int32),
-        ("reserved_", C.c_int32),
+        ("no_leaf_pairs", C.c_int32),
     ]
 
 
@@ -653,7 +653,8 @@ class PySampler:
 
     def __init__(self, settings: PyNutsSettings, model: _Model, *, device=0, waves_per_chain=0, chain_offset=0,
                  n_local_chains=0, stream=None, store_draws=True, evals_per_launch=0, start_paused=False, manual=False,
-                 staging=None, no_register_kernel=False, no_stream_cache=False, graph_steps=0, host_groups=0, host_persist=None):
+                 staging=None, no_register_kernel=False, no_stream_cache=False, graph_steps=0, host_groups=0, host_persist=None,
+                 no_leaf_pairs=False):
         L = lib()
         la = _Launch()
         L.nphip_launch_defaults(C.byref(la))
@@ -668,6 +669,7 @@ class PySampler:
         la.manual = int(bool(manual))
         la.no_register_kernel = int(bool(no_register_kernel))
         la.no_stream_cache = int(bool(no_stream_cache))
+        la.no_leaf_pairs = int(bool(no_leaf_pairs))
         la.graph_steps = int(graph_steps)
         la.host_groups = int(host_groups)
         if host_persist is None:

@@ -177,6 +177,7 @@ struct Args {
     int32_t stream_cache; // 1: memory-resident fused kernel with the cursor's loads cached in VGPRs (NV < 0 instantiations)
     int32_t sig_lds;      // 1: memory-resident kernels with W >= 8 keep the chain's sigma^2 in (dynamic) LDS
     int32_t lean;         // 1: lean register-resident kernel (W = 8, reg_nv chunks per wave, sigma^2 in dynamic LDS)
+    int32_t no_leaf_pairs; // 1: register-resident leaves are never taken two at a time (launch option; Machine::run)
     int32_t max_evals;    // fused: evaluations per chain this launch
     int32_t have_result;  // callbacks: geval/ueval hold the answer to the pending request
     unsigned long long* counters;  // [0] chains done, [1] chains in error, [2] chains that entered PH_WAIT_HOST (cumulative)

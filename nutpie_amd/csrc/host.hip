@@ -956,6 +956,7 @@ bool nphip_sampler::setup() {
     s.low_rank_metric = lrm ? 1 : 0;
 
     args.sig_lds = geo.sig_lds ? 1 : 0;
+    args.no_leaf_pairs = launch.no_leaf_pairs != 0 ? 1 : 0;
 
     if (!dalloc(&args.ctl, n)) return false;
     if (!dalloc(&args.qpool, n * args.nqpool * 2 * ld)) return false;

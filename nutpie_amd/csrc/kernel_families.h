@@ -94,6 +94,13 @@ inline constexpr KernelFamily kDenseResident = {Family::dense_resident, false, f
 
 inline constexpr KernelFamily kFamilies[] = {kW1One, kW1, kW1Wide, kW1Lr, kRing, kRingLr, kLean4, kLean8, kMemory, kMemoryCached, kRemoteW1, kRemoteWn, kDenseResident};
 
+// Chunk counts per lane at which the one-wave fused kernels with the diagonal metric (kW1, kW1Wide) take the two leaves of a level-0 pair in one
+// trip (kernels.hip: Machine::pair_first): bit NV of the mask.  Measured per chunk count against the single leaf: profiles/leaf_pairs_d1000.txt.
+#ifndef NPHIP_LEAF_PAIRS_NV_MASK
+#define NPHIP_LEAF_PAIRS_NV_MASK 0x1FC
+#endif
+constexpr bool leaf_pairs(int W, int NV) { return W == 1 && NV >= 2 && NV <= 8 && ((NPHIP_LEAF_PAIRS_NV_MASK >> NV) & 1) != 0; }
+
 inline constexpr int kWideMaxChains = 1024;   // k_advance<..., WIDE>: a job that brings at most one wave per SIMD
 // waves per chain of the memory-resident kernels beyond the register families; measured at D = 10 000: W = 8 (5.5 M leapfrogs/s) beats 4 (5.0) and 16 (3.6)
 inline constexpr int kMemoryWaves = 8;

@@ -2198,21 +2198,140 @@ struct Machine {
     // multinomial merge of the waiting sub-tree of level k into T: keep T's draw w.p. w_T / (w_A + w_T)
     __device__ __forceinline__ void merge_level(Hot& H, int32_t j, int32_t d, int32_t k, nphip_u32x4& blk, int32_t& blk_id, double& T_wm, int64_t& T_we,
                                                 int32_t& T_q, double& T_U, double& T_E, int32_t& T_idx) {
-        double sm; int64_t se;
         // (the merged sub-tree's buffer is free again unless its draw survives as T's: the caller sets T's bit when it stores T)
         // (everything about the waiting sub-tree is read up front: one LDS round trip, not a second one behind the comparison)
         const int32_t A_q = rfl(c->sub_q[k]), A_idx = rfl(c->sub_idx[k]);
         const double A_U = c->sub_U[k], A_E = c->sub_E[k];
+        merge_record(H, j, d, k, blk, blk_id, A_q, A_idx, A_U, A_E, c->sub_wm[k], c->sub_we[k], T_wm, T_we, T_q, T_U, T_E, T_idx);
+    }
+    // ... with the waiting sub-tree's record handed in (a pair trip keeps leaf A's in registers)
+    __device__ __forceinline__ void merge_record(Hot& H, int32_t j, int32_t d, int32_t k, nphip_u32x4& blk, int32_t& blk_id, int32_t A_q, int32_t A_idx,
+                                                 double A_U, double A_E, double A_wm, int64_t A_we, double& T_wm, int64_t& T_we,
+                                                 int32_t& T_q, double& T_U, double& T_E, int32_t& T_idx) {
+        double sm; int64_t se;
         H.sub_used &= ~(1u << A_q);
-        nphip_w_add(c->sub_wm[k], c->sub_we[k], T_wm, T_we, &sm, &se);
+        nphip_w_add(A_wm, A_we, T_wm, T_we, &sm, &se);
         const bool take = merge_uniform_hot(H, j, d, k, blk, blk_id) * sm < nphip_w_rel(T_wm, T_we, se);
         if (!take) { T_q = A_q; T_U = A_U; T_E = A_E; T_idx = A_idx; }
         T_wm = sm; T_we = se;
     }
 
-    // returns true when an out-of-line (rare) path ran
-    __device__ __forceinline__ bool leaf_reg(RegsT& X, Hot& H, int32_t& end_code_out) {
+    // ---- pair trip: the two leaves of a level-0 pair, A = j (odd) and B = j + 1, in one pass through the leaf (leaf_reg<true>).
+    // An odd leaf closes no merge: it registers itself as a one-leaf sub-tree, and which buffers it writes and which the next leaf
+    // gets depend on j alone.  So B's leapfrog starts right behind A's, and the scalars of both leaves — energies, the exp of the
+    // collector and of the multinomial weight, the division of the symmetric collector — are computed together behind ONE wave
+    // reduction: A's values in the lower half of the lanes, B's in the upper half.  A's leapfrog also leaves out what only an even
+    // leaf uses: the level-0 criterion and the (pold, rold) copies it reads.  The same operations on the same operands per value,
+    // in leaf order where order matters (the collector sums): the same bits.  One wave per chain, fused, diagonal metric, the ring.
+    static constexpr bool PAIRS = FUSED && !LEAN && !REMOTE && !LR && !NORING && nphip::leaf_pairs(W, NV);
+    struct PairA {
+        int32_t nleaf, idx_cur, srcq, srcp, newq, newp;   // the control words as A found them (A diverged: the draw ends as if B had never been taken)
+        uint32_t sub_used;
+        double accK, accL;                                // this lane's part of A's kinetic energy and log density
+    };
+    // leapfrog A, its memory effects and the control updates leaf_reg + issue_leaf_hot make for an odd leaf that did not diverge
+    __device__ __forceinline__ void pair_first(RegsT& X, Hot& H, PairA& a) {
+        constexpr int nk = NVX;
+        const int32_t j = H.nleaf + 1, dir = H.dir, idx_new = H.idx_cur + dir;
+        a.nleaf = H.nleaf; a.idx_cur = H.idx_cur; a.srcq = H.srcq; a.srcp = H.srcp; a.newq = H.newq; a.newp = H.newp; a.sub_used = H.sub_used;
+#ifdef NPHIP_PROFILE
+        const int64_t tp0 = (int64_t)__builtin_readcyclecounter();
+#endif
+        if (X.reg_q != H.srcq) {
+            const double* q = Q(H.srcq);
+#pragma unroll
+            for (int k = 0; k < NVX; ++k) if (k < nk) X.q[k] = ld2(q, ridx(k));
+            regs_grad(X);
+        }
+        if (X.reg_p != H.srcp) load_slot(H.srcp, X.p, X.r);
+        if (!X.sig_ok) {
+#pragma unroll
+            for (int k = 0; k < NVX; ++k) if (k < nk) X.s[k] = ld2(sig2, ridx(k));
+            X.sig_ok = true;
+        }
+        if (j == 1) { X.ring_leaf0 = -1; X.ring_leaf1 = -1; }
+        NPHIP_PHASE_FENCE();
+        const double eps = (double)dir * H.step;
+        const double h = 0.5 * eps;
+        if (idx_new == -1) {  // first backward step: rho' = p'
+#pragma unroll
+            for (int k = 0; k < NVX; ++k) if (k < nk) { X.r[k].x = -0.0; X.r[k].y = -0.0; }
+        }
+        double2 z[NVX];
+#pragma unroll
+        for (int k = 0; k < NVX; ++k) if (k < nk) {
+            X.p[k].x = fma(h, X.g[k].x, X.p[k].x);
+            X.p[k].y = fma(h, X.g[k].y, X.p[k].y);
+            X.q[k].x = fma(eps, X.s[k].x * X.p[k].x, X.q[k].x);
+            X.q[k].y = fma(eps, X.s[k].y * X.p[k].y, X.q[k].y);
+            const double2 mu = par_mu(ridx(k));
+            z[k].x = X.q[k].x - mu.x;
+            z[k].y = X.q[k].y - mu.y;
+        }
+        publish_edges(z);
+        double2 accK = {0.0, 0.0}, accL = {0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < NVX; ++k) if (k < nk) {
+            double2 aa, b01, gg;
+            double b2, edge_zl, edge_zr;
+            par_ab(ridx(k), aa, b01, b2);
+            edge_pair(z, k, edge_zl, edge_zr);
+            const double zl = wave_shr1(z[k].y, edge_zl);
+            const double zr = wave_shl1(z[k].x, edge_zr);
+            double tx = aa.x * z[k].x;
+            tx = fma(b01.x, zl, tx);
+            tx = fma(b01.y, z[k].y, tx);
+            double ty = aa.y * z[k].y;
+            ty = fma(b01.y, z[k].x, ty);
+            ty = fma(b2, zr, ty);
+            gg.x = -tx;
+            gg.y = -ty;
+            accL.x = fma(z[k].x, gg.x, accL.x);
+            accL.y = fma(z[k].y, gg.y, accL.y);
+            X.g[k] = gg;
+            X.p[k].x = fma(h, gg.x, X.p[k].x);
+            X.p[k].y = fma(h, gg.y, X.p[k].y);
+            X.r[k].x = X.r[k].x + X.p[k].x;   // (rho in place: no copy of the source state — an odd leaf checks no criterion)
+            X.r[k].y = X.r[k].y + X.p[k].y;
+            accK.x = fma(X.p[k].x, X.s[k].x * X.p[k].x, accK.x);
+            accK.y = fma(X.p[k].y, X.s[k].y * X.p[k].y, accK.y);
+        }
+        a.accK = accK.x + accK.y;
+        a.accL = accL.x + accL.y;
+        X.reg_q = H.newq;
+        X.reg_p = H.newp;
+        X.dirty_qg = true;
+        X.dirty_pr = true;
+        // memory effects, all decided by j: the ring, q always (an odd leaf is its own sub-tree's candidate), (p, rho) where a level >= 2 merge reads them
+        if ((j & 3) == 1) { ring_write(0, X.p, X.r); X.ring_leaf0 = j; }
+        store_state(X, true, (j & 7) == 1);
+        // leaf A is counted, the cursor moves to it, it waits as the level-0 sub-tree (its record stays in registers), leaf B is issued
+        H.nleaf = j;
+        H.n_steps += 1;
+        H.srcq = a.newq; H.srcp = a.newp; H.idx_cur = idx_new;
+        H.sub_used |= 1u << a.newq;
+        issue_leaf_hot(H);
+#ifdef NPHIP_PROFILE
+        c->prof[0] += (int64_t)__builtin_readcyclecounter() - tp0;
+#endif
+    }
+    // exp(x) from its parts as nphip_exp_scale computes it, with the range cases as selects: the lanes of a pair hold different arguments
+    static __device__ __forceinline__ double exp_scale_select(double x, double p, double k) {
+        const int ki = (int)k;
+        const int k1 = ki / 2, k2 = ki - k1;
+        double e = (p * nphip_pow2i(k1)) * nphip_pow2i(k2);   // (out of range: bits that the selects below replace)
+        e = x < -745.2 ? 0.0 : e;
+        e = x > 709.782712893384 ? (double)INFINITY : e;
+        return e;
+    }
+
+    // returns true when an out-of-line (rare) path ran.  pair (PAIRS only): leaf j (odd) first, then leaf j + 1 as below; *a_ended: the draw ended at leaf j.
+    // (One body for both forms, the pair's first leaf a block in front of it: a second copy of the leaf in the loop of leaves makes the allocator spill.)
+    __device__ __forceinline__ bool leaf_reg(RegsT& X, Hot& H, int32_t& end_code_out, const bool pair_ = false, bool* a_ended = nullptr) {
         constexpr int nk = NVX;  // the register kernels are instantiated per exact chunk count
+        const bool PAIR = PAIRS && pair_;
+        PairA pa = {};
+        if (PAIR) { pair_first(X, H, pa); NPHIP_PHASE_FENCE(); }
         const int32_t j = H.nleaf + 1, d = H.depth, dir = H.dir;
         const int db = dir > 0 ? 1 : 0;
         const int32_t idx_new = H.idx_cur + dir;
@@ -2431,7 +2550,14 @@ struct Machine {
 #endif
         NPHIP_PHASE_FENCE();
         double v4[4] = {accK.x + accK.y, accL.x + accL.y, accE.x + accE.y, accS.x + accS.y};
-        rsum(v4);
+        double vA[2] = {0.0, 0.0};
+        if (PAIR) {   // one reduction for both leaves (eight values: each gets the additions of the contract's order)
+            double v8[8] = {v4[0], v4[1], v4[2], v4[3], pa.accK, pa.accL, 0.0, 0.0};
+            rsum(v8);
+            v4[0] = v8[0]; v4[1] = v8[1]; v4[2] = v8[2]; v4[3] = v8[3]; vA[0] = v8[4]; vA[1] = v8[5];
+        } else {
+            rsum(v4);
+        }
         NPHIP_PHASE_FENCE();
 #ifdef NPHIP_PROFILE
         const int64_t tp2 = (int64_t)__builtin_readcyclecounter();
@@ -2441,6 +2567,20 @@ struct Machine {
         const bool turn0 = (v4[2] < 0.0) || (v4[3] < 0.0);
         if (REMOTE && code_remote < 0) { X.dirty_qg = X.dirty_pr = false; hot_save(H); finish_chain(PH_ERROR, CE_FATAL_LOGP); return true; }
         // ---- NutsTree::extend / merge_into, unrolled (same decisions as cont_tree)
+        double A_U = 0.0, A_E = 0.0, A_dE = 0.0;
+        if (PAIR) {   // leaf A first
+            const double K_A = 0.5 * vA[0], lp_A = 0.5 * vA[1];
+            const bool ok_A = isfinite(lp_A);
+            A_U = -lp_A; A_E = K_A + A_U; A_dE = A_E - H.H0;
+            if (!ok_A || (A_dE > H.max_ee) || !isfinite(A_dE)) {
+                // the draw ends at A exactly as the single leaf ends it: counted once, the cursor and the pending leapfrog as A found them
+                H.idx_cur = pa.idx_cur; H.srcq = pa.srcq; H.srcp = pa.srcp; H.newq = pa.newq; H.newp = pa.newp; H.sub_used = pa.sub_used;
+                X.dirty_qg = X.dirty_pr = false; hot_save(H);
+                end_code_out = end_code(true, false, FUSED, ok_A, !REMOTE, FUSED);
+                *a_ended = true;
+                return true;
+            }
+        }
         H.nleaf += 1;
         H.n_steps += 1;
         const bool ok = isfinite(lp) && (!REMOTE || code_remote == 0);
@@ -2450,7 +2590,32 @@ struct Machine {
         int64_t T_we = 0;
         nphip_u32x4 mrg_blk = {{0u, 0u, 0u, 0u}};
         int32_t mrg_id = -1;
-        {
+        double A_wm = 1.0;
+        int64_t A_we = 0;
+        if constexpr (PAIRS) {
+            // one exp chain and one division for both leaves: lanes 0..31 carry A's energy error, lanes 32..63 B's (B diverged: its
+            // lanes compute on whatever dE is and are not read; a leaf by itself: A's lanes likewise).  Per lane the operations of the single leaf below.
+            if (PAIR || !diverged) {
+            const double x = lane < 32 ? -A_dE : -dE, xc = x > 1e9 ? 1e9 : (x < -1e9 ? -1e9 : x);
+            double wm, kk;
+            nphip_exp_parts(xc, &wm, &kk);
+            const double e = exp_scale_select(x, wm, kk);
+            const double a = e < 1.0 ? e : 1.0;
+            const double sym = 2.0 * a / (1.0 + e);
+            if (PAIR) {
+                A_wm = readlane_f64(wm, 0);
+                A_we = (int64_t)readlane_f64(kk, 0);
+                H.acc += readlane_f64(a, 0);
+                H.acc_sym += readlane_f64(sym, 0);
+            }
+            if (!diverged) {
+                T_wm = readlane_f64(wm, 32);
+                T_we = (int64_t)readlane_f64(kk, 32);
+                H.acc += readlane_f64(a, 32);
+                H.acc_sym += readlane_f64(sym, 32);
+            }
+            }
+        } else {
             if (!diverged) {
                 // one exp serves the collector and the leaf's multinomial weight (its (p, k) parts)
                 const double x = -dE, xc = x > 1e9 ? 1e9 : (x < -1e9 ? -1e9 : x);
@@ -2525,7 +2690,8 @@ struct Machine {
             { const int64_t t_ = (int64_t)__builtin_readcyclecounter(); c->prof[k == 0 ? 9 : 10] += t_ - tq; tq = t_; }
 #endif
             NPHIP_PHASE_FENCE();
-            merge_level(H, j, d, k, mrg_blk, mrg_id, T_wm, T_we, T_q, T_U, T_E, T_idx);
+            if (PAIR && k == 0) merge_record(H, j, d, 0, mrg_blk, mrg_id, pa.newq, pa.idx_cur + dir, A_U, A_E, A_wm, A_we, T_wm, T_we, T_q, T_U, T_E, T_idx);
+            else merge_level(H, j, d, k, mrg_blk, mrg_id, T_wm, T_we, T_q, T_U, T_E, T_idx);
             NPHIP_PHASE_FENCE();
 #ifdef NPHIP_PROFILE
             { const int64_t t_ = (int64_t)__builtin_readcyclecounter(); c->prof[11] += t_ - tq; tq = t_; }
@@ -3915,7 +4081,18 @@ struct Machine {
 #endif
                 if (NV > 0) {
                     if (LEAN) { lean_end = leaf_lean(lrs, X, H); rare = lean_end != 0; }
-                    else rare = leaf_reg(X, H, end_code_);
+                    else {
+                        // an odd leaf of a doubling that has an even one behind it, and budget for both: the pair trip (nothing of a pair crosses a launch boundary)
+                        bool pair = false;
+                        if constexpr (PAIRS) pair = (H.nleaf & 1) == 0 && H.depth >= 1 && budget >= 1 && A.no_leaf_pairs == 0;
+                        bool a_ended = false;
+                        if (pair) --budget;
+                        rare = leaf_reg(X, H, end_code_, pair, &a_ended);
+                        if (a_ended) ++budget;   // leaf B was never taken: its unit goes back
+#ifdef NPHIP_PROFILE
+                        if (pair && !a_ended) { c->prof[3] += 1; c->prof[4] += 1; }
+#endif
+                    }
                 } else {
                     double lp = 0.0;
                     int64_t code = 0;
