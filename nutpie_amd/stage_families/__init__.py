@@ -2,7 +2,8 @@
 
 One :class:`Family` record per family, in its own module next to the functions that build its nodes; ``FAMILIES`` is the table the front
 end (``nutpie_amd.symbolic``: the generator, ``gradient``, ``evaluate``, ``Model.compile``) and the library cache (``nutpie_amd.density``)
-ask instead of naming a family.  Adding a family = one module with one record, and one entry in ``FAMILIES``."""
+and the torch tracer (``nutpie_amd.torch_trace``) ask instead of naming a family.  Adding a family = one module with one record, and one
+entry in ``FAMILIES``."""
 
 from __future__ import annotations
 
@@ -20,6 +21,10 @@ def _no_lengths(payload) -> set[int]:
 
 def _no_limit(nodes, waves_per_chain):
     return waves_per_chain
+
+
+def _declines(*_):
+    return NotImplemented
 
 
 @dataclasses.dataclass(frozen=True)
@@ -59,6 +64,16 @@ class Family:
     series_lengths: Callable = _no_lengths
     #: results may be too long for the LDS of the generated expand function (``Model._finish`` then checks, and expands on the host)
     long_results: bool = True
+    #: base name of a torch op (``cumsum``, ``linalg_cholesky``, the family's own ``nutpie_amd::`` custom ops) -> ``rule(c)``: the lowering
+    #: the torch tracer asks BEFORE its own table, the families in table order.  ``c`` is the tracer's rule context (``c.it`` the
+    #: interpreter, ``c.args`` / ``c.kwargs`` the node's evaluated arguments, ``c.name`` / ``c.base`` the op's names); a rule returns the
+    #: node's value, or ``NotImplemented`` to decline, and the tracer goes on to the next rule of that name (``cumsum`` along a short
+    #: axis).  A rule uses of the interpreter ``it.sym``, ``it.move``, ``it.dim``, ``it.index``, ``it.broadcast``, ``it.m``,
+    #: ``it.fresh_name`` and the attributes ``it.torch`` and ``it.whole``, and the values of ``nutpie_amd.trace_values``.
+    torch_rules: dict[str, Callable] = dataclasses.field(default_factory=dict)
+    #: ``torch_matmul(it, a, b, sa, sb) -> value | NotImplemented``: a product ``a @ b`` (shapes ``sa``, ``sb``, at least one operand
+    #: traced) the family has a stage for; the tracer asks before it multiplies element-wise and sums
+    torch_matmul: Callable = _declines
 
 
 def read_part(n, name: str, array: str, j: str):

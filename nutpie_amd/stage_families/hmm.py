@@ -10,8 +10,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from nutpie_amd.expr import Dim, Expr, _bcast
+from nutpie_amd.expr import Dim, Expr, _bcast, _segsum
 from nutpie_amd.stage_families import Family, np_part, read_part
+from nutpie_amd.trace_values import UnsupportedTorchOp, _numel, _Sym
 
 _HMMOPS = ("hmm_fwd", "hmm_bwd")
 MAX_HMM_STATES = 16   # a lane keeps its column (row) of the transition matrix in registers, a group of up to 16 lanes owns a series
@@ -195,6 +196,110 @@ def _series_lengths(payload) -> set[int]:
     return {R * T * K, R * T, T}
 
 
+# ---- the torch side: what nutpie_amd.torch_trace asks through FAMILY.torch_rules (torch is imported inside the functions)
+def _hmm_traced(it, log_emission, transition, initial) -> _Sym:
+    """nutpie_amd::hmm_marginal onto the IR's HMM stage: the leading axes of ``log_emission`` are the series"""
+    le = it.sym(log_emission)
+    if len(le.shape) < 2:
+        raise UnsupportedTorchOp("hmm_marginal: log_emission is [..., T, K]")
+    T, K = le.shape[-2:]
+    R = _numel(le.shape[:-2])
+    P_s, pi_s = it.sym(transition), it.sym(initial)
+    if _numel(P_s.shape) != K * K or tuple(P_s.shape[-2:]) != (K, K) or _numel(pi_s.shape) != K:
+        raise UnsupportedTorchOp("hmm_marginal: one K x K transition matrix and K initial weights per chain (a matrix per series or per step is not compiled)")
+    logE = _bcast(le.expr, it.dim(R * T * K))
+    P = _bcast(P_s.expr, it.dim(K * K))
+    pi = pi_s.expr if pi_s.expr.dim is None else _bcast(pi_s.expr, it.dim(K))
+    steps = it.dim(R * T)
+    F = _hmm_forward(logE, P, pi, R, T, K, steps, "hmm_marginal")
+    if R == 1:
+        return _Sym(_hmm_lpdf(F, steps), le.shape[:-2])
+    per_step = Expr("hmm_ll", (F,), steps, F.payload)
+    return _Sym(_segsum(per_step, it.index(np.arange(R * T) // T, R * T, R)), le.shape[:-2])
+
+
+_HMM_OP = None
+
+
+def _hmm_marginal_op():
+    """``nutpie_amd::hmm_marginal(log_emission, transition, initial)`` (``transition`` and ``initial`` broadcast against the leading
+    axes of ``log_emission``): a torch custom op — one node of a ``make_fx`` trace, which the tracer maps onto the IR's HMM stage —
+    with a sequential eager implementation in log space and the forward-backward formulas as its autograd"""
+    global _HMM_OP
+    if _HMM_OP is not None:
+        return _HMM_OP
+    import torch
+
+    def forward_loop(logE, P, pi):
+        with torch.no_grad():
+            lead, K = logE.shape[:-2], logE.shape[-1]
+            P, pi = P.expand(*lead, K, K), pi.expand(*lead, K)
+            logP = torch.log(P)
+            la = [torch.log(pi) + logE[..., 0, :]]
+            for t in range(1, logE.shape[-2]):
+                la.append(torch.logsumexp(la[-1].unsqueeze(-1) + logP, dim=-2) + logE[..., t, :])
+            return torch.stack(la, dim=-2)
+
+    @torch.library.custom_op("nutpie_amd::hmm_marginal", mutates_args=(), schema="(Tensor log_emission, Tensor transition, Tensor initial) -> Tensor")
+    def op(log_emission, transition, initial):
+        return torch.logsumexp(forward_loop(log_emission, transition, initial)[..., -1, :], dim=-1)
+
+    @op.register_fake
+    def _(log_emission, transition, initial):
+        return log_emission.new_empty(log_emission.shape[:-2])
+
+    def setup_context(ctx, inputs, output):
+        ctx.save_for_backward(*inputs, output)
+
+    def backward(ctx, g):
+        logE, P0, pi0, ll = ctx.saved_tensors
+        la = forward_loop(logE, P0, pi0)
+        T, K = logE.shape[-2:]
+        P = P0.expand(*logE.shape[:-2], K, K)
+        lb = [torch.zeros_like(la[..., 0, :])]          # log beta, last step first
+        for t in range(T - 1, 0, -1):
+            lb.append(torch.logsumexp(torch.log(P) + (logE[..., t, :] + lb[-1]).unsqueeze(-2), dim=-1))
+        lb = torch.stack(lb[::-1], dim=-2)
+        ll_ = ll[..., None, None]
+        g_ = g[..., None, None]
+        g_logE = g_ * torch.exp(la + lb - ll_)                                   # the smoothed state probabilities
+        # d / d P[i][j] = sum_{t >= 1} alpha_{t-1}[i] e_t[j] beta_t[j] / likelihood (zero for T = 1); d / d pi[k] = e_0[k] beta_0[k] / likelihood
+        pair = la[..., :-1, :, None] + (logE + lb)[..., 1:, None, :] - ll[..., None, None, None]
+        g_P = g_ * torch.exp(pair).sum(dim=-3)
+        g_pi = g[..., None] * torch.exp(logE[..., 0, :] + lb[..., 0, :] - ll[..., None])
+        return g_logE, g_P.sum_to_size(P0.shape), g_pi.sum_to_size(pi0.shape)
+
+    op.register_autograd(backward, setup_context=setup_context)
+    _HMM_OP = op
+    return op
+
+
+def hmm_marginal(log_emission, transition, initial):
+    """The log-likelihood of a hidden Markov model with the state summed out, one value per series: ``log_emission[..., T, K]`` the
+    log density of observation t under state k (every element of the leading axes its own series), ``transition[K, K]`` with row i
+    the weights of the next state given state i, ``initial[K]`` — both non-negative, neither has to sum to one, and both may carry
+    leading axes that broadcast against those of ``log_emission`` (the chains of a batched density: ``transition[:, None]`` against
+    ``log_emission[chains, series, T, K]``).  Returns ``[...]``; the caller sums over the series.  Eager: a sequential loop in log
+    space with the forward-backward formulas as its autograd; traced (``torch_trace.trace``, ``from_torch_density(compile=True)``): the
+    IR's HMM stage, run on the GPU by ``csrc/chain_hmm.h`` (K <= 16, one matrix per chain).  A hand-written Python loop over t in a
+    traced function is not recognised: it stays on the general path and unrolls into T K^2 terms."""
+    import torch
+
+    log_emission = torch.as_tensor(log_emission)
+    K = log_emission.shape[-1]
+    transition = torch.as_tensor(transition, dtype=log_emission.dtype, device=log_emission.device)
+    initial = torch.as_tensor(initial, dtype=log_emission.dtype, device=log_emission.device)
+    if initial.dim() == 0:
+        initial = initial.expand(K)
+    if tuple(transition.shape[-2:]) != (K, K) or initial.shape[-1] != K:
+        raise ValueError(f"hmm_marginal: transition is [..., {K}, {K}] and initial [..., {K}] for log_emission [..., T, {K}]")
+    return _hmm_marginal_op()(log_emission, transition, initial)
+
+
+def _torch_hmm_marginal(c):
+    return _hmm_traced(c.it, c.args[0], c.args[1], c.args[2])
+
+
 FAMILY = Family(name="hmm", ops=_HMMOPS, readers=("hmm_part", "hmm_ll"), header="chain_hmm.h", call=_call, read=_read, numpy=_numpy,
                 adjoint={"hmm_ll": _ll_adjoint}, refusal="second derivatives of the HMM stages (hmm_state_prob carries no gradient)",
-                check=_check, series_lengths=_series_lengths)
+                check=_check, series_lengths=_series_lengths, torch_rules={"hmm_marginal": _torch_hmm_marginal})

@@ -9,10 +9,13 @@ payload = (R, T, m, masked)."""
 
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
-from nutpie_amd.expr import _HALF_LOG_2PI, Dim, Expr, _bcast, log
+from nutpie_amd.expr import _HALF_LOG_2PI, Dim, Expr, _bcast, _segsum, log
 from nutpie_amd.stage_families import Family, np_part, read_part
+from nutpie_amd.trace_values import UnsupportedTorchOp, _numel, _Sym
 
 _KALOPS = ("kalman_fwd", "kalman_bwd")
 MAX_KALMAN_STATE = 8   # a lane keeps its row of the state covariance in registers, a group of up to 8 lanes owns a series
@@ -260,7 +263,175 @@ def _series_lengths(payload) -> set[int]:
     return {R * T * m, R * T, T}
 
 
+# ---- the torch side: what nutpie_amd.torch_trace asks through FAMILY.torch_rules (torch is imported inside the functions)
+def _kalman_traced(it, y, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None) -> _Sym:
+    """nutpie_amd::kalman_marginal onto the IR's Kalman filter stage: the leading axes of ``y`` are the series"""
+    ys, zs = it.sym(y), it.sym(design)
+    if len(ys.shape) < 1 or len(zs.shape) < 2 or tuple(zs.shape[:-1]) != tuple(ys.shape):
+        raise UnsupportedTorchOp("kalman_marginal: y is [..., T] and design [..., T, m]")
+    T, m = ys.shape[-1], zs.shape[-1]
+    R = _numel(ys.shape[:-1])
+    on = lambda sym_, n: _bcast(sym_.expr, it.dim(n))      # noqa: E731  (a scalar for all elements, or the value on the dimension of n elements)
+    mats = [it.sym(v) for v in (transition, state_cov, init_cov)]
+    a0 = it.sym(init_mean)
+    if any(_numel(v.shape) != m * m or tuple(v.shape[-2:]) != (m, m) for v in mats) or _numel(a0.shape) != m:
+        raise UnsupportedTorchOp("kalman_marginal: one m x m transition, state_cov, init_cov and one init_mean per chain (a matrix per series or per step is not compiled)")
+    hs = it.sym(obs_var)
+    if _numel(hs.shape) not in (1, R * T):
+        raise UnsupportedTorchOp("kalman_marginal: obs_var is a scalar or [..., T]")
+    obs = None
+    if observed is not None:
+        o = it.sym(observed).expr
+        if o.op == "const":
+            if o.payload == 0.0:
+                return _Sym(Expr.const(0.0), ys.shape[:-1])
+        elif o.op != "data":
+            raise UnsupportedTorchOp("kalman_marginal: observed is constant data")
+        else:
+            obs = _bcast(o, it.dim(R * T))
+    Tm, Q, P0 = (on(v, m * m) for v in mats)
+    F = _kalman_forward(on(ys, R * T), on(zs, R * T * m), on(hs, R * T), Tm, Q, on(a0, m), P0, obs, R, T, m, "kalman_marginal")
+    terms = _kalman_terms(F)
+    if R == 1:
+        return _Sym(terms.sum(), ys.shape[:-1])
+    return _Sym(_segsum(terms, it.index(np.arange(R * T) // T, R * T, R)), ys.shape[:-1])
+
+
+_KALMAN_OP = None
+
+
+def _kalman_marginal_op():
+    """``nutpie_amd::kalman_marginal``: a torch custom op — one node of a ``make_fx`` trace, which the tracer maps onto the IR's Kalman
+    filter stage — with a sequential eager implementation and the adjoint of the filter as its autograd"""
+    global _KALMAN_OP
+    if _KALMAN_OP is not None:
+        return _KALMAN_OP
+    import torch
+
+    log_2pi = math.log(2.0 * math.pi)
+
+    def flat(y, Z, h, Tm, Q, a0, P0, observed):
+        """every operand with the leading axes of y, flattened into one"""
+        lead, T, m = y.shape[:-1], y.shape[-1], Z.shape[-1]
+        ex = lambda v, *tail: v.expand(*lead, *tail).reshape(-1, *tail)      # noqa: E731
+        seen = torch.ones_like(y) if observed is None else (observed != 0).to(y.dtype)
+        return ex(y, T), ex(Z, T, m), ex(h, T), ex(Tm, m, m), ex(Q, m, m), ex(a0, m), ex(P0, m, m), ex(seen, T)
+
+    def filter_loop(y, Z, h, Tm, Q, a0, P0, seen):
+        T = y.shape[-1]
+        a, P = a0, P0
+        apred, Ppred, vs, Fs = [], [], [], []
+        for t in range(T):
+            z, s_ = Z[:, t], seen[:, t]
+            apred.append(a)
+            Ppred.append(P)
+            M = torch.einsum("bij,bj->bi", P, z)
+            v = s_ * (y[:, t] - (z * a).sum(-1))
+            F = torch.where(s_ != 0, h[:, t] + (z * M).sum(-1), torch.ones_like(v))
+            K = s_[:, None] * M / F[:, None]
+            af = a + K * v[:, None]
+            Pf = P - K[:, :, None] * M[:, None, :]
+            vs.append(v)
+            Fs.append(F)
+            a = torch.einsum("bik,bk->bi", Tm, af)
+            P = Q + torch.einsum("bik,bkl,bjl->bij", Tm, Pf, Tm)
+        return torch.stack(apred, 1), torch.stack(Ppred, 1), torch.stack(vs, 1), torch.stack(Fs, 1)
+
+    @torch.library.custom_op("nutpie_amd::kalman_marginal", mutates_args=(),
+                             schema="(Tensor y, Tensor design, Tensor obs_var, Tensor transition, Tensor state_cov, Tensor init_mean, Tensor init_cov, Tensor? observed) -> Tensor")
+    def op(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed):
+        with torch.no_grad():
+            ops = flat(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed)
+            _, _, v, F = filter_loop(*ops)
+            return (-0.5 * ops[7] * (log_2pi + torch.log(F) + v * v / F)).sum(-1).reshape(y.shape[:-1])
+
+    @op.register_fake
+    def _(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed):
+        return y.new_empty(y.shape[:-1])
+
+    def setup_context(ctx, inputs, output):
+        ctx.save_for_backward(*[v for v in inputs if v is not None])
+        ctx.masked = inputs[7] is not None
+
+    def backward(ctx, g):
+        saved = list(ctx.saved_tensors)
+        raw = saved[:7] + [saved[7] if ctx.masked else None]
+        y, Z, h, Tm, Q, a0, P0, seen = flat(*raw)
+        apred, Ppred, vs, Fs = filter_loop(y, Z, h, Tm, Q, a0, P0, seen)
+        T = y.shape[-1]
+        gb = g.reshape(-1, 1)
+        vbar = gb * seen * (-vs / Fs)
+        Fbar = gb * seen * (-0.5) * (1.0 / Fs - vs * vs / (Fs * Fs))
+        ybar, hbar, Zbar = torch.zeros_like(y), torch.zeros_like(h), torch.zeros_like(Z)
+        Tb, Qb = torch.zeros_like(Tm), torch.zeros_like(Q)
+        ab, Pb = torch.zeros_like(a0), torch.zeros_like(P0)
+        for t in range(T - 1, -1, -1):
+            z, s_, a, P, v, F = Z[:, t], seen[:, t], apred[:, t], Ppred[:, t], vs[:, t], Fs[:, t]
+            M = torch.einsum("bij,bj->bi", P, z)
+            K = s_[:, None] * M / F[:, None]
+            af = a + K * v[:, None]
+            Pf = P - K[:, :, None] * M[:, None, :]
+            if t < T - 1:
+                Qb = Qb + Pb
+                Tb = Tb + torch.einsum("bij,bjl,bkl->bik", Pb, Tm, Pf) + torch.einsum("bji,bjl,blk->bik", Pb, Tm, Pf) + ab[:, :, None] * af[:, None, :]
+                Pfb = torch.einsum("bli,blj,bjk->bik", Tm, Pb, Tm)
+                afb = torch.einsum("bik,bi->bk", Tm, ab)
+            else:
+                Pfb, afb = torch.zeros_like(Pb), torch.zeros_like(ab)
+            Kb = afb * v[:, None] - torch.einsum("bij,bj->bi", Pfb, M)
+            vb = vbar[:, t] + (afb * K).sum(-1)
+            Fb = Fbar[:, t] - (Kb * K).sum(-1) / F
+            Mb = -torch.einsum("bij,bi->bj", Pfb, K) + Kb / F[:, None] + Fb[:, None] * z
+            ybar[:, t], hbar[:, t] = s_ * vb, s_ * Fb
+            Zbar[:, t] = s_[:, None] * (Fb[:, None] * M + torch.einsum("bik,bi->bk", P, Mb) - vb[:, None] * a)
+            ab = afb - (s_ * vb)[:, None] * z
+            Pb = Pfb + (s_[:, None] * Mb)[:, :, None] * z[:, None, :]
+        lead = raw[0].shape[:-1]
+        back = lambda v, like: v.reshape(*lead, *v.shape[1:]).sum_to_size(like.shape)      # noqa: E731
+        return (back(ybar, raw[0]), back(Zbar, raw[1]), back(hbar, raw[2]), back(Tb, raw[3]), back(Qb, raw[4]), back(ab, raw[5]), back(Pb, raw[6]), None)
+
+    op.register_autograd(backward, setup_context=setup_context)
+    _KALMAN_OP = op
+    return op
+
+
+def kalman_marginal(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None):
+    """The log-likelihood of a linear Gaussian state-space model with the state summed out by a Kalman filter, one value per series:
+    ``y[..., T]`` (every element of the leading axes its own series), ``design[..., T, m]`` or ``[m]`` (the same row at every step),
+    ``obs_var[..., T]`` or one number, ``transition[m, m]``, ``state_cov[m, m]``, ``init_mean[m]``, ``init_cov[m, m]`` (the state at
+    t = 0, before the first observation; these four may carry leading axes that broadcast against those of ``y``: the chains of a
+    batched density), ``observed[..., T]`` constant, 0 where the observation is missing.  Returns ``[...]``; the caller sums over the
+    series.  Eager: a sequential loop with the filter's adjoint as its autograd; traced (``torch_trace.trace``,
+    ``from_torch_density(compile=True)``): the IR's Kalman filter stage, run on the GPU by ``csrc/chain_kalman.h`` (m <= 8, one
+    transition matrix per chain).  A hand-written Python loop over t in a traced function is not recognised: it stays on the general
+    path and unrolls into T m^3 terms."""
+    import torch
+
+    y = torch.as_tensor(y)
+    kw = dict(dtype=y.dtype, device=y.device)
+    design, obs_var = torch.as_tensor(design, **kw), torch.as_tensor(obs_var, **kw)
+    m = design.shape[-1] if design.dim() else 1
+    transition, state_cov, init_cov = (torch.as_tensor(v, **kw) for v in (transition, state_cov, init_cov))
+    init_mean = torch.as_tensor(init_mean, **kw)
+    if init_mean.dim() == 0:
+        init_mean = init_mean.expand(m)
+    if y.dim() < 1 or design.dim() < 1 or any(tuple(v.shape[-2:]) != (m, m) for v in (transition, state_cov, init_cov)) or init_mean.shape[-1] != m:
+        raise ValueError(f"kalman_marginal: transition, state_cov, init_cov are [..., {m}, {m}] and init_mean [..., {m}] for design [..., {m}]")
+    try:
+        design = design.expand(*y.shape, m) if design.dim() > 1 else design.expand(*y.shape, m)
+        obs_var = obs_var.expand(y.shape)
+        if observed is not None:
+            observed = torch.as_tensor(observed, **kw).expand(y.shape)
+    except RuntimeError as e:
+        raise ValueError(f"kalman_marginal: design is [..., T, m] or [m], obs_var and observed [..., T] or scalars for y [..., T] ({e})") from None
+    return _kalman_marginal_op()(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed)
+
+
+def _torch_kalman_marginal(c):
+    return _kalman_traced(c.it, *c.args[:8])
+
+
 FAMILY = Family(name="kalman", ops=_KALOPS, readers=("kalman_part",), header="chain_kalman.h", header_deps=("chain_hmm.h",), call=_call,
                 read=read_part, numpy=_numpy, adjoint={"kalman_part": _part_adjoint}, finish=_finish,
                 refusal="second derivatives of the Kalman filter stages (kalman_filtered_state carries no gradient)",
-                check=_check, section=_section, series_lengths=_series_lengths)
+                check=_check, section=_section, series_lengths=_series_lengths, torch_rules={"kalman_marginal": _torch_kalman_marginal})

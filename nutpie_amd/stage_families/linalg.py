@@ -12,6 +12,7 @@ import numpy as np
 
 from nutpie_amd.expr import _HALF_LOG_2PI, Expr, _bcast, elem, log
 from nutpie_amd.stage_families import Family
+from nutpie_amd.trace_values import UnsupportedTorchOp, _is_traced, _numel, _Sym
 
 _MATOPS = ("chol", "trsv", "trsv_t", "trsv_gl", "chol_adj")
 MAX_MATRIX = 32     # the largest K a compiled density factors (8 KB per matrix and chain)
@@ -185,6 +186,72 @@ def _check(nodes, waves_per_chain):
     return 1
 
 
+# ---- the torch side: what nutpie_amd.torch_trace asks through FAMILY.torch_rules (torch is imported inside the functions)
+def _matrix(it, v, what: str) -> tuple[_Sym, int]:
+    """a traced square matrix (leading axes of length one) as a K x K value on its own dimension"""
+    v = it.sym(v)
+    if len(v.shape) < 2 or v.shape[-1] != v.shape[-2] or _numel(v.shape) != v.shape[-1] ** 2:
+        raise UnsupportedTorchOp(f"{what} of a traced matrix of shape {v.shape} (one K x K matrix per chain)")
+    k = v.shape[-1]
+    return _Sym(_bcast(v.expr, it.dim(k * k)), v.shape), k
+
+
+def _cholesky(it, a) -> _Sym:
+    A, k = _matrix(it, a, "cholesky")
+    if k > MAX_MATRIX:
+        raise UnsupportedTorchOp(f"cholesky of a {k} x {k} traced matrix (compiled densities factor up to {MAX_MATRIX} x {MAX_MATRIX})")
+    return _Sym(cholesky(A.expr), A.shape)
+
+
+def _solve_triangular(it, a, b, upper: bool, left: bool) -> _Sym:
+    """A X = B (``left``) or X A = B with a traced triangular A, as ``solve_lower`` of K x N right-hand sides"""
+    if not left:        # X A = B  <=>  A^T X^T = B^T
+        bt = it.move(it.sym(b), lambda t: t.transpose(-1, -2))
+        at = it.move(it.sym(a), lambda t: t.transpose(-1, -2))
+        return it.move(_solve_triangular(it, at, bt, not upper, True), lambda t: t.transpose(-1, -2))
+    if upper:           # U^-1 B = R (R U R)^-1 R B with R the reversal: R U R is lower triangular
+        ar = it.move(it.sym(a), lambda t: t.flip(-1, -2))
+        br = it.move(it.sym(b), lambda t: t.flip(-2))
+        return it.move(_solve_triangular(it, ar, br, False, True), lambda t: t.flip(-2))
+    A, k = _matrix(it, a, "solve_triangular")
+    if k > MAX_MATRIX:
+        raise UnsupportedTorchOp(f"solve_triangular with a {k} x {k} traced matrix (compiled densities solve up to {MAX_MATRIX} x {MAX_MATRIX})")
+    B = it.sym(b)
+    if len(B.shape) < 2 or B.shape[-2] != k:
+        raise UnsupportedTorchOp(f"solve_triangular: right-hand sides of shape {B.shape} for a {k} x {k} matrix")
+    bshape = B.shape
+    batch, n = bshape[:-2], bshape[-1]
+    m = _numel(batch) * n
+    # the right-hand sides as K x (batch, N): every column one of them
+    Bk = it.move(B, lambda t: t.movedim(-2, 0).reshape(k, m))
+    X = _Sym(solve_lower(A.expr, _bcast(Bk.expr, it.dim(k * m))), (k, m))
+    return it.move(X, lambda t: t.reshape(k, *batch, n).movedim(0, -2))
+
+
+def _torch_cholesky(c):
+    # a traced matrix: the Cholesky stage (one chain's K x K matrix)
+    it = c.it
+    L = _cholesky(it, c.args[0])
+    if bool(c.arg(1, "upper", False)):
+        L = it.move(L, lambda t: t.transpose(-1, -2))
+    if c.base == "linalg_cholesky_ex":
+        # (info: 0 — a matrix that is not positive definite makes the density NaN instead of raising)
+        return (L, it.torch.zeros(L.shape[:-2], dtype=it.torch.int32))
+    return L
+
+
+def _torch_solve_triangular(c):
+    # a traced triangular matrix: the triangular solve (lower, left) — other forms through transposes and reversals; a constant
+    # matrix is the tracer's own rule
+    if not _is_traced(c.args[0]):
+        return NotImplemented
+    if bool(c.kwargs.get("unitriangular", False)):
+        raise UnsupportedTorchOp(f"{c.name} with unitriangular=True and a traced matrix")
+    return _solve_triangular(c.it, c.args[0], c.args[1], bool(c.kwargs.get("upper", False)), bool(c.kwargs.get("left", True)))
+
+
 FAMILY = Family(name="linalg", ops=_MATOPS, header="chain_linalg.h", call=_call, numpy=_numpy,
                 adjoint={"chol": _chol_adjoint, "trsv": _trsv_adjoint}, refusal="second derivatives of the matrix and scan stages",
-                check=_check, long_results=False)
+                check=_check, long_results=False,
+                torch_rules={"linalg_cholesky_ex": _torch_cholesky, "linalg_cholesky": _torch_cholesky, "cholesky": _torch_cholesky,
+                             "linalg_solve_triangular": _torch_solve_triangular})

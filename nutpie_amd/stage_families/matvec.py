@@ -10,6 +10,7 @@ import numpy as np
 
 from nutpie_amd.expr import Dim, Expr, _bcast, elem
 from nutpie_amd.stage_families import Family
+from nutpie_amd.trace_values import _is_traced, _numel, _Sym, _X
 
 _MVOPS = ("matvec", "matvec_t")
 MAX_RHS = 16        # the right-hand sides of one product: that many accumulators per row block of a lane
@@ -155,5 +156,46 @@ def _section(n: Expr) -> str:
     return f"stage {n.op}<{n.payload[1]}, {n.payload[2]}> of {n.payload[0]}"
 
 
+# ---- the torch side: what nutpie_amd.torch_trace's matmul asks through FAMILY.torch_matmul
+def _data_matrix_product(it, mat, vec, out_shape, original):
+    torch = it.torch
+    rows, k = int(mat.shape[0]), int(mat.shape[1])
+    # (up to Matrix.STAGE_ABOVE columns the IR unrolls the product over the columns; beyond, `Matrix @` is the data-matrix stage
+    #  of csrc/chain_matvec.h: the matrix is read as data, never expanded into an n k-element product)
+    if not (k > 1 and rows > 1) or isinstance(vec, _X) and not it.whole:
+        return None
+    bv = it.sym(vec)
+    if bv.expr.dim is None or not bool(torch.isfinite(mat).all()):
+        return None
+    name = it.fresh_name(original)
+    m = it.m.matrix(name, mat.to(torch.float64).contiguous().cpu().numpy(), dim=it.dim(rows).name, cols=it.dim(k).name)
+    return _Sym(m @ bv.expr, out_shape)
+
+
+def _torch_matmul(it, a, b, sa, sb):
+    torch = it.torch
+    ca, cb = not _is_traced(a), not _is_traced(b)
+    # a data matrix times a traced vector: the IR's design-matrix form (few columns: one wave-wide sum per column in the gradient;
+    # many: the data-matrix stage); `v @ M` with M[k, n] data is the same product with the transposed matrix
+    if cb and len(sb) == 2 and len(sa) in (1, 2) and _numel(sa) == sb[0] and not ca:
+        r = _data_matrix_product(it, b.t(), a, (sb[1],) if len(sa) == 1 else (1, sb[1]), None)
+        if r is not None:
+            return r
+    if ca and len(sa) == 2 and len(sb) in (1, 2) and _numel(sb) == sa[1] and not cb:
+        r = _data_matrix_product(it, a, b, (sa[0],) if len(sb) == 1 else (sa[0], 1), a)
+        if r is not None:
+            return r
+    # a data matrix times a traced k x R matrix (the classes of a softmax regression; leading axes of length one are the batch's):
+    # one product with R right-hand sides, the n x R result row-major as torch has it
+    if (ca and len(sa) >= 2 and len(sb) >= 2 and sb[-2] == sa[-1] and 2 <= sb[-1] <= MAX_RHS and _numel(sa[:-2]) == 1
+            and _numel(sb[:-2]) == 1 and sa[-2] > 1 and sa[-1] > 1 and not cb and not (isinstance(b, _X) and not it.whole)):
+        bv = it.sym(b)
+        n, k, R = sa[-2], sa[-1], sb[-1]
+        if bv.expr.dim is not None and bool(torch.isfinite(a).all()):
+            m = it.m.matrix(it.fresh_name(a), a.reshape(n, k).to(torch.float64).contiguous().cpu().numpy(), dim=it.dim(n).name, cols=it.dim(k).name)
+            return _Sym(m.times(bv.expr, it.dim(n * R), R), (1,) * (max(len(sa), len(sb)) - 2) + (n, R))
+    return NotImplemented
+
+
 FAMILY = Family(name="matvec", ops=_MVOPS, header="chain_matvec.h", call=_call, numpy=_numpy, adjoint={"matvec": _adjoint, "matvec_t": _adjoint},
-                refusal="second derivatives of the matrix and scan stages", section=_section)
+                refusal="second derivatives of the matrix and scan stages", section=_section, torch_matmul=_torch_matmul)

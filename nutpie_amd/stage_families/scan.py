@@ -11,6 +11,7 @@ import numpy as np
 
 from nutpie_amd.expr import Dim, Expr, _bcast, _segsum, elem, select, where_lt
 from nutpie_amd.stage_families import Family
+from nutpie_amd.trace_values import _numel, _Sym
 
 _SCANOPS = ("scan", "rscan")
 
@@ -139,5 +140,127 @@ def _call(gen, n: Expr) -> str:
             f"({coef}, {a_s}, {gen.store_name[v.id]}, {i_arr}, {i_s}, {gen.store_name[n.id]}, lane);")
 
 
+# ---- the torch side: what nutpie_amd.torch_trace asks through FAMILY.torch_rules (torch is imported inside the functions)
+def _scan_traced(it, a, b: _Sym, init, ax: int) -> _Sym:
+    """x_t = a_t x_{t-1} + b_t along axis ``ax`` of the traced ``b`` (``a``: broadcast against ``b``; ``init``: against ``b`` without
+    that axis): the axis moved last, the elements of the other axes the rows of one scan stage, the result moved back"""
+    shp = b.shape
+    last = len(shp) - 1
+    to_last = (lambda t: t.movedim(ax, -1)) if ax != last else None
+    bm = it.move(b, to_last) if to_last else b
+    T = bm.shape[-1] if bm.shape else 1
+    R = _numel(bm.shape) // T
+    P = it.dim(R * T)
+    a_s = it.sym(a)
+    if _numel(a_s.shape) == 1:
+        a_e = a_s.expr if a_s.expr.dim is None else elem(a_s.expr, 0)
+    else:
+        if ax != last and len(a_s.shape) == len(shp):
+            a_s = it.move(a_s, to_last)
+        a_e = it.broadcast(a_s, bm.shape)
+        a_e = a_e if a_e.dim is None else _bcast(a_e, P)
+    i_s = it.sym(init)
+    rows = None
+    if _numel(i_s.shape) == 1:
+        i_e = i_s.expr if i_s.expr.dim is None else elem(i_s.expr, 0)
+    else:
+        i_e = it.broadcast(i_s, bm.shape[:-1])
+        if i_e.dim is not None:
+            rows = it.dim(R)
+            i_e = _bcast(i_e, rows)
+    x = _Sym(_scan(a_e, _bcast(bm.expr, P), i_e, R, T, rows), bm.shape)
+    return it.move(x, lambda t: t.movedim(-1, ax)) if to_last else x
+
+
+_LR_OP = None
+
+
+def _linear_recurrence_op():
+    """``nutpie_amd::linear_recurrence(a, b, init)`` (time the last axis of ``b``; ``a`` broadcast against ``b``, ``init`` against
+    ``b[..., 0]``): a torch custom op — one node of a ``make_fx`` trace, which the tracer maps onto the IR's scan stage — with a
+    sequential eager implementation and its adjoint as the autograd formula"""
+    global _LR_OP
+    if _LR_OP is not None:
+        return _LR_OP
+    import torch
+
+    def forward_loop(a, b, init):
+        a = a.expand_as(b)
+        prev = init.expand(b.shape[:-1])
+        cols = []
+        for t in range(b.shape[-1]):
+            prev = a[..., t] * prev + b[..., t]
+            cols.append(prev)
+        return torch.stack(cols, dim=-1)
+
+    @torch.library.custom_op("nutpie_amd::linear_recurrence", mutates_args=(), schema="(Tensor a, Tensor b, Tensor init) -> Tensor")
+    def op(a, b, init):
+        return forward_loop(a, b, init)
+
+    @op.register_fake
+    def _(a, b, init):
+        return torch.empty_like(b)
+
+    def setup_context(ctx, inputs, output):
+        a, b, init = inputs
+        ctx.save_for_backward(a, b, init, output)
+
+    def backward(ctx, g):
+        a, b, init, x = ctx.saved_tensors
+        ae = a.expand_as(b)
+        # lambda_t = a_{t+1} lambda_{t+1} + g_t (the adjoint recurrence, run backwards)
+        shifted = torch.cat([ae[..., 1:], torch.zeros_like(ae[..., :1])], dim=-1)
+        lam = forward_loop(shifted.flip(-1), g.flip(-1), torch.zeros((), dtype=g.dtype, device=g.device)).flip(-1)
+        xprev = torch.cat([init.expand(b.shape[:-1]).unsqueeze(-1), x[..., :-1]], dim=-1)
+        ga = (lam * xprev).sum_to_size(a.shape)
+        gi = (ae[..., 0] * lam[..., 0]).sum_to_size(init.shape)
+        return ga, lam.sum_to_size(b.shape), gi
+
+    op.register_autograd(backward, setup_context=setup_context)
+    _LR_OP = op
+    return op
+
+
+# (``nutpie_amd.torch_trace.linear_recurrence``: in this module that name is the expression front end's)
+def torch_linear_recurrence(a, b, init=0.0, dim: int = -1):
+    """``x_t = a_t x_{t-1} + b_t`` along axis ``dim`` of the tensor ``b``, with ``x_{-1} = init``: ``a`` a number or a tensor that
+    broadcasts against ``b``, ``init`` a number or a tensor that broadcasts against ``b`` without that axis (every other element of
+    ``b``'s other axes is its own series).  Eager: a sequential loop with its adjoint as the autograd formula; traced
+    (``torch_trace.trace``, ``from_torch_density(compile=True)``): the IR's scan stage, run on the GPU by ``csrc/chain_scan.h``.
+    Covers a cumulative sum (``a = 1``), an AR(1) path (``a = phi``), a GARCH(1, 1) variance filter and exponential smoothing."""
+    import torch
+
+    b = torch.as_tensor(b)
+    a = torch.as_tensor(a, dtype=b.dtype, device=b.device)
+    init = torch.as_tensor(init, dtype=b.dtype, device=b.device)
+    d = dim % b.dim()
+    if d != b.dim() - 1:
+        b = b.movedim(d, -1)
+        if a.dim() == b.dim():
+            a = a.movedim(d, -1)
+    x = _linear_recurrence_op()(a, b, init)
+    return x.movedim(-1, d) if d != b.dim() - 1 else x
+
+
+def _torch_cumsum(c):
+    # a prefix sum of a traced value along a long axis: the scan stage with a = 1, the axis moved last and the others as rows (a
+    # short axis, or a broadcast scalar, is the tracer's own rule)
+    shp = c.args[0].shape
+    ax = c.arg(1, "dim") % max(len(shp), 1)
+    if (shp[ax] if shp else 1) <= 64:
+        return NotImplemented
+    v = c.it.sym(c.args[0])
+    if v.expr.dim is None:
+        return NotImplemented
+    return _scan_traced(c.it, 1.0, v, 0.0, ax)
+
+
+def _torch_linear_recurrence(c):
+    # nutpie_amd::linear_recurrence (time is the last axis): the scan stage
+    b = c.it.sym(c.args[1])
+    return _scan_traced(c.it, c.args[0], b, c.args[2], len(b.shape) - 1)
+
+
 FAMILY = Family(name="scan", ops=_SCANOPS, header="chain_scan.h", call=_call, numpy=_numpy, adjoint={"scan": _adjoint},
-                refusal="second derivatives of the matrix and scan stages")
+                refusal="second derivatives of the matrix and scan stages",
+                torch_rules={"cumsum": _torch_cumsum, "linear_recurrence": _torch_linear_recurrence})

@@ -29,6 +29,13 @@ when the pieces do not overlap; any other use of ``x`` makes the whole vector on
 
 Anything that cannot be mapped raises :class:`UnsupportedTorchOp` naming the operation; ``from_torch_density(compile="auto")``
 then falls back to the eager device callback and says why.
+
+Rules.  ``_run`` walks the fx graph and knows no operation: the value of a node comes from a RULE, a function of one context object
+(``_Ctx``), found by the node's base name — first in the stage families' ``Family.torch_rules`` (:mod:`nutpie_amd.stage_families`, in
+table order; a family rule returns ``NotImplemented`` to decline, and a product asks ``Family.torch_matmul``), then in this module's
+own table ``_RULES``, which ``@_rule(names...)`` fills (a name registered twice fails at import).  A name in neither table is
+refused.  A new ATen operation is one function under ``@_rule`` in the group it belongs to; what maps onto a stage family (its custom
+ops with their eager loops and autograd included) lives in the family's module, and this module names no family.
 """
 
 from __future__ import annotations
@@ -40,49 +47,18 @@ from typing import Any, Callable
 import numpy as np
 
 from nutpie_amd import symbolic as S
+from nutpie_amd.stage_families import FAMILIES
 from nutpie_amd.symbolic import Expr
 
+# ---- re-exports: the values of a trace (nutpie_amd/trace_values.py) and the torch functions of the stage families, under the names they
+# have always had here
+from nutpie_amd.stage_families.hmm import hmm_marginal  # noqa: F401
+from nutpie_amd.stage_families.kalman import kalman_marginal  # noqa: F401
+from nutpie_amd.stage_families.scan import torch_linear_recurrence as linear_recurrence  # noqa: F401
+from nutpie_amd.trace_values import UnsupportedTorchOp, _Bool, _is_traced, _NeedWholeVector, _numel, _Sym, _X  # noqa: F401
+
 __all__ = ["trace", "traced_model", "UnsupportedTorchOp", "TraceResult", "linear_recurrence", "hmm_marginal", "kalman_marginal"]
-
-
-class UnsupportedTorchOp(NotImplementedError):
-    """The traced function uses an operation (or a form of one) the IR has no counterpart for."""
-
-
-class _NeedWholeVector(Exception):
-    """the position vector is used in a way the partition into parameters cannot express: trace again with x as ONE parameter"""
-
-
-def _numel(shape) -> int:
-    return int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
-
-
-class _Sym:
-    """a traced float tensor: ``expr`` on the dimension of ``numel(shape)`` elements (row-major), or a scalar for all of them"""
-
-    __slots__ = ("expr", "shape")
-
-    def __init__(self, expr: Expr, shape):
-        self.expr, self.shape = expr, tuple(int(v) for v in shape)
-
-
-class _Bool:
-    """a traced boolean tensor: a tree of comparisons of traced values (``gt`` / ``ge`` of an expression against zero, ``not``,
-    ``and``, ``or``)"""
-
-    __slots__ = ("tree", "shape")
-
-    def __init__(self, tree, shape):
-        self.tree, self.shape = tree, tuple(int(v) for v in shape)
-
-
-class _X:
-    """the position vector (or a view of it that keeps all of its elements in order)"""
-
-    __slots__ = ("shape",)
-
-    def __init__(self, shape):
-        self.shape = tuple(int(v) for v in shape)
+# ---- end of the re-exports
 
 
 class TraceResult:
@@ -189,7 +165,7 @@ class _Interp:
 
     # ---- values
     def is_const(self, v) -> bool:
-        return not isinstance(v, (_Sym, _Bool, _X))
+        return not _is_traced(v)
 
     def sym(self, v, shape=None) -> _Sym:
         """any value as a traced float tensor"""
@@ -414,25 +390,10 @@ class _Interp:
         sa, sb = self.shape_of(a), self.shape_of(b)
         if len(sa) == 0 or len(sb) == 0:
             raise UnsupportedTorchOp("matmul with a zero-dimensional operand")
-        # a data matrix times a traced vector: the IR's design-matrix form (few columns: one wave-wide sum per column in the gradient;
-        # many: the data-matrix stage); `v @ M` with M[k, n] data is the same product with the transposed matrix
-        if self.is_const(b) and len(sb) == 2 and len(sa) in (1, 2) and _numel(sa) == sb[0] and not self.is_const(a):
-            r = self._data_matrix_product(b.t(), a, (sb[1],) if len(sa) == 1 else (1, sb[1]), None)
-            if r is not None:
+        for f in FAMILIES:      # a stage family's form of the product (a data matrix times a traced vector or matrix)
+            r = f.torch_matmul(self, a, b, sa, sb)
+            if r is not NotImplemented:
                 return r
-        if self.is_const(a) and len(sa) == 2 and len(sb) in (1, 2) and _numel(sb) == sa[1] and not self.is_const(b):
-            r = self._data_matrix_product(a, b, (sa[0],) if len(sb) == 1 else (sa[0], 1), a)
-            if r is not None:
-                return r
-        # a data matrix times a traced k x R matrix (the classes of a softmax regression; leading axes of length one are the batch's):
-        # one product with R right-hand sides, the n x R result row-major as torch has it
-        if (self.is_const(a) and len(sa) >= 2 and len(sb) >= 2 and sb[-2] == sa[-1] and 2 <= sb[-1] <= S.MAX_RHS and _numel(sa[:-2]) == 1
-                and _numel(sb[:-2]) == 1 and sa[-2] > 1 and sa[-1] > 1 and not self.is_const(b) and not (isinstance(b, _X) and not self.whole)):
-            bv = self.sym(b)
-            n, k, R = sa[-2], sa[-1], sb[-1]
-            if bv.expr.dim is not None and bool(torch.isfinite(a).all()):
-                m = self.m.matrix(self.fresh_name(a), a.reshape(n, k).to(torch.float64).contiguous().cpu().numpy(), dim=self.dim(n).name, cols=self.dim(k).name)
-                return _Sym(m.times(bv.expr, self.dim(n * R), R), (1,) * (max(len(sa), len(sb)) - 2) + (n, R))
         av = a if self.is_const(a) else self.sym(a)
         bv = b if self.is_const(b) else self.sym(b)
         a1 = len(sa) == 1
@@ -448,20 +409,6 @@ class _Interp:
         if b1:
             out = self.move(out, lambda t: t.squeeze(-1))
         return out
-
-    def _data_matrix_product(self, mat, vec, out_shape, original):
-        torch = self.torch
-        rows, k = int(mat.shape[0]), int(mat.shape[1])
-        # (up to Matrix.STAGE_ABOVE columns the IR unrolls the product over the columns; beyond, `Matrix @` is the data-matrix stage
-        #  of csrc/chain_matvec.h: the matrix is read as data, never expanded into an n k-element product)
-        if not (k > 1 and rows > 1) or isinstance(vec, _X) and not self.whole:
-            return None
-        bv = self.sym(vec)
-        if bv.expr.dim is None or not bool(torch.isfinite(mat).all()):
-            return None
-        name = self.fresh_name(original)
-        m = self.m.matrix(name, mat.to(torch.float64).contiguous().cpu().numpy(), dim=self.dim(rows).name, cols=self.dim(k).name)
-        return _Sym(m @ bv.expr, out_shape)
 
     # ---- scatter-adds: out = base + sum of source elements by target
     def scatter_add(self, base, source, target_of_source: np.ndarray) -> _Sym:
@@ -553,419 +500,583 @@ def _pow_traced(x: Expr, y: Expr) -> Expr:
     return S.exp(y * S.log(x))
 
 
-def _matrix(it: _Interp, v, what: str) -> tuple[_Sym, int]:
-    """a traced square matrix (leading axes of length one) as a K x K value on its own dimension"""
-    v = it.sym(v)
-    if len(v.shape) < 2 or v.shape[-1] != v.shape[-2] or _numel(v.shape) != v.shape[-1] ** 2:
-        raise UnsupportedTorchOp(f"{what} of a traced matrix of shape {v.shape} (one K x K matrix per chain)")
-    k = v.shape[-1]
-    return _Sym(S._bcast(v.expr, it.dim(k * k)), v.shape), k
-
-
-def _cholesky(it: _Interp, a) -> _Sym:
-    A, k = _matrix(it, a, "cholesky")
-    if k > S.MAX_MATRIX:
-        raise UnsupportedTorchOp(f"cholesky of a {k} x {k} traced matrix (compiled densities factor up to {S.MAX_MATRIX} x {S.MAX_MATRIX})")
-    return _Sym(S.cholesky(A.expr), A.shape)
-
-
-def _solve_triangular(it: _Interp, a, b, upper: bool, left: bool) -> _Sym:
-    """A X = B (``left``) or X A = B with a traced triangular A, as ``solve_lower`` of K x N right-hand sides"""
-    if not left:        # X A = B  <=>  A^T X^T = B^T
-        bt = it.move(it.sym(b), lambda t: t.transpose(-1, -2))
-        at = it.move(it.sym(a), lambda t: t.transpose(-1, -2))
-        return it.move(_solve_triangular(it, at, bt, not upper, True), lambda t: t.transpose(-1, -2))
-    if upper:           # U^-1 B = R (R U R)^-1 R B with R the reversal: R U R is lower triangular
-        ar = it.move(it.sym(a), lambda t: t.flip(-1, -2))
-        br = it.move(it.sym(b), lambda t: t.flip(-2))
-        return it.move(_solve_triangular(it, ar, br, False, True), lambda t: t.flip(-2))
-    A, k = _matrix(it, a, "solve_triangular")
-    if k > S.MAX_MATRIX:
-        raise UnsupportedTorchOp(f"solve_triangular with a {k} x {k} traced matrix (compiled densities solve up to {S.MAX_MATRIX} x {S.MAX_MATRIX})")
-    B = it.sym(b)
-    if len(B.shape) < 2 or B.shape[-2] != k:
-        raise UnsupportedTorchOp(f"solve_triangular: right-hand sides of shape {B.shape} for a {k} x {k} matrix")
-    bshape = B.shape
-    batch, n = bshape[:-2], bshape[-1]
-    m = _numel(batch) * n
-    # the right-hand sides as K x (batch, N): every column one of them
-    Bk = it.move(B, lambda t: t.movedim(-2, 0).reshape(k, m))
-    X = _Sym(S.solve_lower(A.expr, S._bcast(Bk.expr, it.dim(k * m))), (k, m))
-    return it.move(X, lambda t: t.reshape(k, *batch, n).movedim(0, -2))
-
-
-def _scan_traced(it: _Interp, a, b: _Sym, init, ax: int) -> _Sym:
-    """x_t = a_t x_{t-1} + b_t along axis ``ax`` of the traced ``b`` (``a``: broadcast against ``b``; ``init``: against ``b`` without
-    that axis): the axis moved last, the elements of the other axes the rows of one scan stage, the result moved back"""
-    shp = b.shape
-    last = len(shp) - 1
-    to_last = (lambda t: t.movedim(ax, -1)) if ax != last else None
-    bm = it.move(b, to_last) if to_last else b
-    T = bm.shape[-1] if bm.shape else 1
-    R = _numel(bm.shape) // T
-    P = it.dim(R * T)
-    a_s = it.sym(a)
-    if _numel(a_s.shape) == 1:
-        a_e = a_s.expr if a_s.expr.dim is None else S.elem(a_s.expr, 0)
-    else:
-        if ax != last and len(a_s.shape) == len(shp):
-            a_s = it.move(a_s, to_last)
-        a_e = it.broadcast(a_s, bm.shape)
-        a_e = a_e if a_e.dim is None else S._bcast(a_e, P)
-    i_s = it.sym(init)
-    rows = None
-    if _numel(i_s.shape) == 1:
-        i_e = i_s.expr if i_s.expr.dim is None else S.elem(i_s.expr, 0)
-    else:
-        i_e = it.broadcast(i_s, bm.shape[:-1])
-        if i_e.dim is not None:
-            rows = it.dim(R)
-            i_e = S._bcast(i_e, rows)
-    x = _Sym(S._scan(a_e, S._bcast(bm.expr, P), i_e, R, T, rows), bm.shape)
-    return it.move(x, lambda t: t.movedim(-1, ax)) if to_last else x
-
-
-_LR_OP = None
-
-
-def _linear_recurrence_op():
-    """``nutpie_amd::linear_recurrence(a, b, init)`` (time the last axis of ``b``; ``a`` broadcast against ``b``, ``init`` against
-    ``b[..., 0]``): a torch custom op — one node of a ``make_fx`` trace, which the tracer maps onto the IR's scan stage — with a
-    sequential eager implementation and its adjoint as the autograd formula"""
-    global _LR_OP
-    if _LR_OP is not None:
-        return _LR_OP
-    import torch
-
-    def forward_loop(a, b, init):
-        a = a.expand_as(b)
-        prev = init.expand(b.shape[:-1])
-        cols = []
-        for t in range(b.shape[-1]):
-            prev = a[..., t] * prev + b[..., t]
-            cols.append(prev)
-        return torch.stack(cols, dim=-1)
-
-    @torch.library.custom_op("nutpie_amd::linear_recurrence", mutates_args=(), schema="(Tensor a, Tensor b, Tensor init) -> Tensor")
-    def op(a, b, init):
-        return forward_loop(a, b, init)
-
-    @op.register_fake
-    def _(a, b, init):
-        return torch.empty_like(b)
-
-    def setup_context(ctx, inputs, output):
-        a, b, init = inputs
-        ctx.save_for_backward(a, b, init, output)
-
-    def backward(ctx, g):
-        a, b, init, x = ctx.saved_tensors
-        ae = a.expand_as(b)
-        # lambda_t = a_{t+1} lambda_{t+1} + g_t (the adjoint recurrence, run backwards)
-        shifted = torch.cat([ae[..., 1:], torch.zeros_like(ae[..., :1])], dim=-1)
-        lam = forward_loop(shifted.flip(-1), g.flip(-1), torch.zeros((), dtype=g.dtype, device=g.device)).flip(-1)
-        xprev = torch.cat([init.expand(b.shape[:-1]).unsqueeze(-1), x[..., :-1]], dim=-1)
-        ga = (lam * xprev).sum_to_size(a.shape)
-        gi = (ae[..., 0] * lam[..., 0]).sum_to_size(init.shape)
-        return ga, lam.sum_to_size(b.shape), gi
-
-    op.register_autograd(backward, setup_context=setup_context)
-    _LR_OP = op
-    return op
-
-
-def linear_recurrence(a, b, init=0.0, dim: int = -1):
-    """``x_t = a_t x_{t-1} + b_t`` along axis ``dim`` of the tensor ``b``, with ``x_{-1} = init``: ``a`` a number or a tensor that
-    broadcasts against ``b``, ``init`` a number or a tensor that broadcasts against ``b`` without that axis (every other element of
-    ``b``'s other axes is its own series).  Eager: a sequential loop with its adjoint as the autograd formula; traced
-    (:func:`trace`, ``from_torch_density(compile=True)``): the IR's scan stage, run on the GPU by ``csrc/chain_scan.h``.
-    Covers a cumulative sum (``a = 1``), an AR(1) path (``a = phi``), a GARCH(1, 1) variance filter and exponential smoothing."""
-    import torch
-
-    b = torch.as_tensor(b)
-    a = torch.as_tensor(a, dtype=b.dtype, device=b.device)
-    init = torch.as_tensor(init, dtype=b.dtype, device=b.device)
-    d = dim % b.dim()
-    if d != b.dim() - 1:
-        b = b.movedim(d, -1)
-        if a.dim() == b.dim():
-            a = a.movedim(d, -1)
-    x = _linear_recurrence_op()(a, b, init)
-    return x.movedim(-1, d) if d != b.dim() - 1 else x
-
-
-def _hmm_traced(it: _Interp, log_emission, transition, initial) -> _Sym:
-    """nutpie_amd::hmm_marginal onto the IR's HMM stage: the leading axes of ``log_emission`` are the series"""
-    le = it.sym(log_emission)
-    if len(le.shape) < 2:
-        raise UnsupportedTorchOp("hmm_marginal: log_emission is [..., T, K]")
-    T, K = le.shape[-2:]
-    R = _numel(le.shape[:-2])
-    P_s, pi_s = it.sym(transition), it.sym(initial)
-    if _numel(P_s.shape) != K * K or tuple(P_s.shape[-2:]) != (K, K) or _numel(pi_s.shape) != K:
-        raise UnsupportedTorchOp("hmm_marginal: one K x K transition matrix and K initial weights per chain (a matrix per series or per step is not compiled)")
-    logE = S._bcast(le.expr, it.dim(R * T * K))
-    P = S._bcast(P_s.expr, it.dim(K * K))
-    pi = pi_s.expr if pi_s.expr.dim is None else S._bcast(pi_s.expr, it.dim(K))
-    steps = it.dim(R * T)
-    F = S._hmm_forward(logE, P, pi, R, T, K, steps, "hmm_marginal")
-    if R == 1:
-        return _Sym(S._hmm_lpdf(F, steps), le.shape[:-2])
-    per_step = Expr("hmm_ll", (F,), steps, F.payload)
-    return _Sym(S._segsum(per_step, it.index(np.arange(R * T) // T, R * T, R)), le.shape[:-2])
-
-
-_HMM_OP = None
-
-
-def _hmm_marginal_op():
-    """``nutpie_amd::hmm_marginal(log_emission, transition, initial)`` (``transition`` and ``initial`` broadcast against the leading
-    axes of ``log_emission``): a torch custom op — one node of a ``make_fx`` trace, which the tracer maps onto the IR's HMM stage —
-    with a sequential eager implementation in log space and the forward-backward formulas as its autograd"""
-    global _HMM_OP
-    if _HMM_OP is not None:
-        return _HMM_OP
-    import torch
-
-    def forward_loop(logE, P, pi):
-        with torch.no_grad():
-            lead, K = logE.shape[:-2], logE.shape[-1]
-            P, pi = P.expand(*lead, K, K), pi.expand(*lead, K)
-            logP = torch.log(P)
-            la = [torch.log(pi) + logE[..., 0, :]]
-            for t in range(1, logE.shape[-2]):
-                la.append(torch.logsumexp(la[-1].unsqueeze(-1) + logP, dim=-2) + logE[..., t, :])
-            return torch.stack(la, dim=-2)
-
-    @torch.library.custom_op("nutpie_amd::hmm_marginal", mutates_args=(), schema="(Tensor log_emission, Tensor transition, Tensor initial) -> Tensor")
-    def op(log_emission, transition, initial):
-        return torch.logsumexp(forward_loop(log_emission, transition, initial)[..., -1, :], dim=-1)
-
-    @op.register_fake
-    def _(log_emission, transition, initial):
-        return log_emission.new_empty(log_emission.shape[:-2])
-
-    def setup_context(ctx, inputs, output):
-        ctx.save_for_backward(*inputs, output)
-
-    def backward(ctx, g):
-        logE, P0, pi0, ll = ctx.saved_tensors
-        la = forward_loop(logE, P0, pi0)
-        T, K = logE.shape[-2:]
-        P = P0.expand(*logE.shape[:-2], K, K)
-        lb = [torch.zeros_like(la[..., 0, :])]          # log beta, last step first
-        for t in range(T - 1, 0, -1):
-            lb.append(torch.logsumexp(torch.log(P) + (logE[..., t, :] + lb[-1]).unsqueeze(-2), dim=-1))
-        lb = torch.stack(lb[::-1], dim=-2)
-        ll_ = ll[..., None, None]
-        g_ = g[..., None, None]
-        g_logE = g_ * torch.exp(la + lb - ll_)                                   # the smoothed state probabilities
-        # d / d P[i][j] = sum_{t >= 1} alpha_{t-1}[i] e_t[j] beta_t[j] / likelihood (zero for T = 1); d / d pi[k] = e_0[k] beta_0[k] / likelihood
-        pair = la[..., :-1, :, None] + (logE + lb)[..., 1:, None, :] - ll[..., None, None, None]
-        g_P = g_ * torch.exp(pair).sum(dim=-3)
-        g_pi = g[..., None] * torch.exp(logE[..., 0, :] + lb[..., 0, :] - ll[..., None])
-        return g_logE, g_P.sum_to_size(P0.shape), g_pi.sum_to_size(pi0.shape)
-
-    op.register_autograd(backward, setup_context=setup_context)
-    _HMM_OP = op
-    return op
-
-
-def hmm_marginal(log_emission, transition, initial):
-    """The log-likelihood of a hidden Markov model with the state summed out, one value per series: ``log_emission[..., T, K]`` the
-    log density of observation t under state k (every element of the leading axes its own series), ``transition[K, K]`` with row i
-    the weights of the next state given state i, ``initial[K]`` — both non-negative, neither has to sum to one, and both may carry
-    leading axes that broadcast against those of ``log_emission`` (the chains of a batched density: ``transition[:, None]`` against
-    ``log_emission[chains, series, T, K]``).  Returns ``[...]``; the caller sums over the series.  Eager: a sequential loop in log
-    space with the forward-backward formulas as its autograd; traced (:func:`trace`, ``from_torch_density(compile=True)``): the
-    IR's HMM stage, run on the GPU by ``csrc/chain_hmm.h`` (K <= 16, one matrix per chain).  A hand-written Python loop over t in a
-    traced function is not recognised: it stays on the general path and unrolls into T K^2 terms."""
-    import torch
-
-    log_emission = torch.as_tensor(log_emission)
-    K = log_emission.shape[-1]
-    transition = torch.as_tensor(transition, dtype=log_emission.dtype, device=log_emission.device)
-    initial = torch.as_tensor(initial, dtype=log_emission.dtype, device=log_emission.device)
-    if initial.dim() == 0:
-        initial = initial.expand(K)
-    if tuple(transition.shape[-2:]) != (K, K) or initial.shape[-1] != K:
-        raise ValueError(f"hmm_marginal: transition is [..., {K}, {K}] and initial [..., {K}] for log_emission [..., T, {K}]")
-    return _hmm_marginal_op()(log_emission, transition, initial)
-
-
-def _kalman_traced(it: _Interp, y, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None) -> _Sym:
-    """nutpie_amd::kalman_marginal onto the IR's Kalman filter stage: the leading axes of ``y`` are the series"""
-    ys, zs = it.sym(y), it.sym(design)
-    if len(ys.shape) < 1 or len(zs.shape) < 2 or tuple(zs.shape[:-1]) != tuple(ys.shape):
-        raise UnsupportedTorchOp("kalman_marginal: y is [..., T] and design [..., T, m]")
-    T, m = ys.shape[-1], zs.shape[-1]
-    R = _numel(ys.shape[:-1])
-    on = lambda sym_, n: S._bcast(sym_.expr, it.dim(n))      # noqa: E731  (a scalar for all elements, or the value on the dimension of n elements)
-    mats = [it.sym(v) for v in (transition, state_cov, init_cov)]
-    a0 = it.sym(init_mean)
-    if any(_numel(v.shape) != m * m or tuple(v.shape[-2:]) != (m, m) for v in mats) or _numel(a0.shape) != m:
-        raise UnsupportedTorchOp("kalman_marginal: one m x m transition, state_cov, init_cov and one init_mean per chain (a matrix per series or per step is not compiled)")
-    hs = it.sym(obs_var)
-    if _numel(hs.shape) not in (1, R * T):
-        raise UnsupportedTorchOp("kalman_marginal: obs_var is a scalar or [..., T]")
-    obs = None
-    if observed is not None:
-        o = it.sym(observed).expr
-        if o.op == "const":
-            if o.payload == 0.0:
-                return _Sym(Expr.const(0.0), ys.shape[:-1])
-        elif o.op != "data":
-            raise UnsupportedTorchOp("kalman_marginal: observed is constant data")
-        else:
-            obs = S._bcast(o, it.dim(R * T))
-    Tm, Q, P0 = (on(v, m * m) for v in mats)
-    F = S._kalman_forward(on(ys, R * T), on(zs, R * T * m), on(hs, R * T), Tm, Q, on(a0, m), P0, obs, R, T, m, "kalman_marginal")
-    terms = S._kalman_terms(F)
-    if R == 1:
-        return _Sym(terms.sum(), ys.shape[:-1])
-    return _Sym(S._segsum(terms, it.index(np.arange(R * T) // T, R * T, R)), ys.shape[:-1])
-
-
-_KALMAN_OP = None
-
-
-def _kalman_marginal_op():
-    """``nutpie_amd::kalman_marginal``: a torch custom op — one node of a ``make_fx`` trace, which the tracer maps onto the IR's Kalman
-    filter stage — with a sequential eager implementation and the adjoint of the filter as its autograd"""
-    global _KALMAN_OP
-    if _KALMAN_OP is not None:
-        return _KALMAN_OP
-    import torch
-
-    log_2pi = math.log(2.0 * math.pi)
-
-    def flat(y, Z, h, Tm, Q, a0, P0, observed):
-        """every operand with the leading axes of y, flattened into one"""
-        lead, T, m = y.shape[:-1], y.shape[-1], Z.shape[-1]
-        ex = lambda v, *tail: v.expand(*lead, *tail).reshape(-1, *tail)      # noqa: E731
-        seen = torch.ones_like(y) if observed is None else (observed != 0).to(y.dtype)
-        return ex(y, T), ex(Z, T, m), ex(h, T), ex(Tm, m, m), ex(Q, m, m), ex(a0, m), ex(P0, m, m), ex(seen, T)
-
-    def filter_loop(y, Z, h, Tm, Q, a0, P0, seen):
-        T = y.shape[-1]
-        a, P = a0, P0
-        apred, Ppred, vs, Fs = [], [], [], []
-        for t in range(T):
-            z, s_ = Z[:, t], seen[:, t]
-            apred.append(a)
-            Ppred.append(P)
-            M = torch.einsum("bij,bj->bi", P, z)
-            v = s_ * (y[:, t] - (z * a).sum(-1))
-            F = torch.where(s_ != 0, h[:, t] + (z * M).sum(-1), torch.ones_like(v))
-            K = s_[:, None] * M / F[:, None]
-            af = a + K * v[:, None]
-            Pf = P - K[:, :, None] * M[:, None, :]
-            vs.append(v)
-            Fs.append(F)
-            a = torch.einsum("bik,bk->bi", Tm, af)
-            P = Q + torch.einsum("bik,bkl,bjl->bij", Tm, Pf, Tm)
-        return torch.stack(apred, 1), torch.stack(Ppred, 1), torch.stack(vs, 1), torch.stack(Fs, 1)
-
-    @torch.library.custom_op("nutpie_amd::kalman_marginal", mutates_args=(),
-                             schema="(Tensor y, Tensor design, Tensor obs_var, Tensor transition, Tensor state_cov, Tensor init_mean, Tensor init_cov, Tensor? observed) -> Tensor")
-    def op(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed):
-        with torch.no_grad():
-            ops = flat(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed)
-            _, _, v, F = filter_loop(*ops)
-            return (-0.5 * ops[7] * (log_2pi + torch.log(F) + v * v / F)).sum(-1).reshape(y.shape[:-1])
-
-    @op.register_fake
-    def _(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed):
-        return y.new_empty(y.shape[:-1])
-
-    def setup_context(ctx, inputs, output):
-        ctx.save_for_backward(*[v for v in inputs if v is not None])
-        ctx.masked = inputs[7] is not None
-
-    def backward(ctx, g):
-        saved = list(ctx.saved_tensors)
-        raw = saved[:7] + [saved[7] if ctx.masked else None]
-        y, Z, h, Tm, Q, a0, P0, seen = flat(*raw)
-        apred, Ppred, vs, Fs = filter_loop(y, Z, h, Tm, Q, a0, P0, seen)
-        T = y.shape[-1]
-        gb = g.reshape(-1, 1)
-        vbar = gb * seen * (-vs / Fs)
-        Fbar = gb * seen * (-0.5) * (1.0 / Fs - vs * vs / (Fs * Fs))
-        ybar, hbar, Zbar = torch.zeros_like(y), torch.zeros_like(h), torch.zeros_like(Z)
-        Tb, Qb = torch.zeros_like(Tm), torch.zeros_like(Q)
-        ab, Pb = torch.zeros_like(a0), torch.zeros_like(P0)
-        for t in range(T - 1, -1, -1):
-            z, s_, a, P, v, F = Z[:, t], seen[:, t], apred[:, t], Ppred[:, t], vs[:, t], Fs[:, t]
-            M = torch.einsum("bij,bj->bi", P, z)
-            K = s_[:, None] * M / F[:, None]
-            af = a + K * v[:, None]
-            Pf = P - K[:, :, None] * M[:, None, :]
-            if t < T - 1:
-                Qb = Qb + Pb
-                Tb = Tb + torch.einsum("bij,bjl,bkl->bik", Pb, Tm, Pf) + torch.einsum("bji,bjl,blk->bik", Pb, Tm, Pf) + ab[:, :, None] * af[:, None, :]
-                Pfb = torch.einsum("bli,blj,bjk->bik", Tm, Pb, Tm)
-                afb = torch.einsum("bik,bi->bk", Tm, ab)
-            else:
-                Pfb, afb = torch.zeros_like(Pb), torch.zeros_like(ab)
-            Kb = afb * v[:, None] - torch.einsum("bij,bj->bi", Pfb, M)
-            vb = vbar[:, t] + (afb * K).sum(-1)
-            Fb = Fbar[:, t] - (Kb * K).sum(-1) / F
-            Mb = -torch.einsum("bij,bi->bj", Pfb, K) + Kb / F[:, None] + Fb[:, None] * z
-            ybar[:, t], hbar[:, t] = s_ * vb, s_ * Fb
-            Zbar[:, t] = s_[:, None] * (Fb[:, None] * M + torch.einsum("bik,bi->bk", P, Mb) - vb[:, None] * a)
-            ab = afb - (s_ * vb)[:, None] * z
-            Pb = Pfb + (s_[:, None] * Mb)[:, :, None] * z[:, None, :]
-        lead = raw[0].shape[:-1]
-        back = lambda v, like: v.reshape(*lead, *v.shape[1:]).sum_to_size(like.shape)      # noqa: E731
-        return (back(ybar, raw[0]), back(Zbar, raw[1]), back(hbar, raw[2]), back(Tb, raw[3]), back(Qb, raw[4]), back(ab, raw[5]), back(Pb, raw[6]), None)
-
-    op.register_autograd(backward, setup_context=setup_context)
-    _KALMAN_OP = op
-    return op
-
-
-def kalman_marginal(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None):
-    """The log-likelihood of a linear Gaussian state-space model with the state summed out by a Kalman filter, one value per series:
-    ``y[..., T]`` (every element of the leading axes its own series), ``design[..., T, m]`` or ``[m]`` (the same row at every step),
-    ``obs_var[..., T]`` or one number, ``transition[m, m]``, ``state_cov[m, m]``, ``init_mean[m]``, ``init_cov[m, m]`` (the state at
-    t = 0, before the first observation; these four may carry leading axes that broadcast against those of ``y``: the chains of a
-    batched density), ``observed[..., T]`` constant, 0 where the observation is missing.  Returns ``[...]``; the caller sums over the
-    series.  Eager: a sequential loop with the filter's adjoint as its autograd; traced (:func:`trace`,
-    ``from_torch_density(compile=True)``): the IR's Kalman filter stage, run on the GPU by ``csrc/chain_kalman.h`` (m <= 8, one
-    transition matrix per chain).  A hand-written Python loop over t in a traced function is not recognised: it stays on the general
-    path and unrolls into T m^3 terms."""
-    import torch
-
-    y = torch.as_tensor(y)
-    kw = dict(dtype=y.dtype, device=y.device)
-    design, obs_var = torch.as_tensor(design, **kw), torch.as_tensor(obs_var, **kw)
-    m = design.shape[-1] if design.dim() else 1
-    transition, state_cov, init_cov = (torch.as_tensor(v, **kw) for v in (transition, state_cov, init_cov))
-    init_mean = torch.as_tensor(init_mean, **kw)
-    if init_mean.dim() == 0:
-        init_mean = init_mean.expand(m)
-    if y.dim() < 1 or design.dim() < 1 or any(tuple(v.shape[-2:]) != (m, m) for v in (transition, state_cov, init_cov)) or init_mean.shape[-1] != m:
-        raise ValueError(f"kalman_marginal: transition, state_cov, init_cov are [..., {m}, {m}] and init_mean [..., {m}] for design [..., {m}]")
-    try:
-        design = design.expand(*y.shape, m) if design.dim() > 1 else design.expand(*y.shape, m)
-        obs_var = obs_var.expand(y.shape)
-        if observed is not None:
-            observed = torch.as_tensor(observed, **kw).expand(y.shape)
-    except RuntimeError as e:
-        raise ValueError(f"kalman_marginal: design is [..., T, m] or [m], obs_var and observed [..., T] or scalars for y [..., T] ({e})") from None
-    return _kalman_marginal_op()(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed)
-
-
 def _scalar(v) -> float:
     if hasattr(v, "item"):
         return float(v.item())
     return float(v)
 
 
+def _to_host(v):
+    import torch
+
+    if isinstance(v, torch.Tensor):
+        return v.detach().cpu()
+    if isinstance(v, (list, tuple)):
+        return type(v)(_to_host(t) for t in v)
+    return v
+
+
+def _any_traced(v) -> bool:
+    if isinstance(v, (list, tuple)):
+        return any(_any_traced(t) for t in v)
+    return _is_traced(v)
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the rules
+class _Ctx:
+    """What a rule is handed: the interpreter ``it``, the fx ``node``, its target ``tgt`` with the names ``name`` (as torch prints it)
+    and ``base`` (the overload packet's, the key of the tables), and the node's ``args`` / ``kwargs`` with every fx node replaced by its value."""
+
+    __slots__ = ("it", "node", "tgt", "name", "base", "args", "kwargs")
+
+    def __init__(self, it: _Interp, node, tgt, name: str, base: str, args, kwargs):
+        self.it, self.node, self.tgt, self.name, self.base, self.args, self.kwargs = it, node, tgt, name, base, args, kwargs
+
+    def arg(self, i: int, key: str, default=None):
+        """argument ``i``, which the schema also takes by the keyword ``key``"""
+        return self.args[i] if len(self.args) > i else self.kwargs.get(key, default)
+
+    def B(self, a, b, f) -> _Sym:
+        return self.it.binary(a, b, f)
+
+    def U(self, a, f) -> _Sym:
+        return self.it.unary(a, f)
+
+    def alpha(self) -> float:
+        return _scalar(self.kwargs.get("alpha", 1))
+
+
+#: base name -> ``rule(c: _Ctx) -> the node's value``: the tracer's own lowerings, asked after the stage families'
+#: (``Family.torch_rules``); a name in neither table is refused
+_RULES: dict[str, Callable] = {}
+
+
+def _rule(*names: str):
+    def register(f):
+        for n in names:
+            assert n not in _RULES, f"two rules for {n}"
+            _RULES[n] = f
+        return f
+
+    return register
+
+
+def _lower(c: _Ctx):
+    """the value of the node of ``c``: the first family rule of its base name that does not decline, else the tracer's own"""
+    for f in FAMILIES:
+        rule = f.torch_rules.get(c.base)
+        if rule is not None:
+            r = rule(c)
+            if r is not NotImplemented:
+                return r
+    rule = _RULES.get(c.base)
+    if rule is None:
+        raise UnsupportedTorchOp(f"{c.name} (no counterpart in the expression IR)")
+    return rule(c)
+
+
+# ---------------- the position vector: pieces become parameters
+def _x_piece(it: _Interp, lo: int, hi: int, scalar: bool, out_shape) -> _Sym:
+    return _Sym(it.piece(lo, hi, scalar).expr, out_shape)
+
+
+def _x_rule(c: _Ctx):
+    """an operation on the position vector while it is partitioned (``args[0]`` an ``_X``, the trace not ``whole``): tried before the tables"""
+    it, base, args, kwargs = c.it, c.base, c.args, c.kwargs
+    torch = it.torch
+    a0 = args[0]
+    D = it.n_dim
+    shp = a0.shape
+    ax = [i for i, s in enumerate(shp) if s != 1]
+    ax = ax[0] if ax else len(shp) - 1
+    if base == "select":
+        d_, idx = args[1] % len(shp), args[2]
+        if d_ == ax and D > 0:
+            idx = idx % D
+            return _x_piece(it, idx, idx + 1, True, tuple(s for i, s in enumerate(shp) if i != d_))
+        if shp[d_] == 1:
+            return _X(tuple(s for i, s in enumerate(shp) if i != d_))
+    elif base == "slice":
+        d_ = (args[1] if len(args) > 1 else 0) % len(shp)
+        lo = args[2] if len(args) > 2 and args[2] is not None else 0
+        hi = args[3] if len(args) > 3 and args[3] is not None else shp[d_]
+        step = args[4] if len(args) > 4 else 1
+        lo, hi, _ = slice(lo, hi, step).indices(shp[d_])
+        if d_ == ax and step == 1:
+            if lo == 0 and hi == D:
+                return a0
+            if hi > lo:
+                return _x_piece(it, lo, hi, False, tuple((hi - lo) if i == d_ else s for i, s in enumerate(shp)))
+            raise UnsupportedTorchOp("an empty slice of x")
+        if d_ != ax and lo == 0 and hi == shp[d_] and step == 1:
+            return a0
+    elif base in ("split", "split_with_sizes", "unbind", "chunk"):
+        probe = c.tgt(torch.arange(D, dtype=torch.int64).reshape(shp), *args[1:], **kwargs)
+        outs = []
+        ok = True
+        for p in probe:
+            f = p.reshape(-1)
+            if f.numel() == 0 or not torch.equal(f, torch.arange(int(f[0]), int(f[0]) + f.numel())):
+                ok = False
+                break
+            outs.append((int(f[0]), int(f[0]) + f.numel(), tuple(p.shape)))
+        if ok:
+            return [_x_piece(it, lo, hi, _numel(s) == 1 and base == "unbind", s) for lo, hi, s in outs]
+    elif base in ("view", "_unsafe_view", "reshape", "squeeze", "unsqueeze", "alias", "detach", "clone", "contiguous", "_to_copy", "lift_fresh_copy", "flatten", "expand"):
+        probe = c.tgt(torch.zeros(shp, dtype=torch.float64), *args[1:], **kwargs)
+        if probe.numel() == D and sum(1 for s in probe.shape if s != 1) <= 1:
+            return _X(tuple(probe.shape))
+    raise _NeedWholeVector(f"x is used by {c.name}")
+
+
+# ---------------- element-wise arithmetic
+@_rule("add")
+def _add(c):
+    al = c.alpha()
+    return c.B(c.args[0], c.args[1], lambda x, y: x + (y if al == 1 else al * y))
+
+
+@_rule("sub")
+def _sub(c):
+    al = c.alpha()
+    return c.B(c.args[0], c.args[1], lambda x, y: x - (y if al == 1 else al * y))
+
+
+@_rule("rsub")
+def _rsub(c):
+    al = c.alpha()
+    return c.B(c.args[0], c.args[1], lambda x, y: y - (x if al == 1 else al * x))
+
+
+_UNARY = {
+    "neg": lambda x: -x,
+    "reciprocal": lambda x: 1.0 / x,
+    "square": lambda x: x * x,
+    "abs": S.absolute,
+    "rsqrt": lambda x: 1.0 / S.sqrt(x),
+    "log2": lambda x: S.log(x) * (1.0 / math.log(2.0)),
+    "log10": lambda x: S.log(x) * (1.0 / math.log(10.0)),
+    "exp2": lambda x: S.exp(x * math.log(2.0)),
+    "logit": lambda x: S.log(x) - S.log1p(-x),
+    "relu": lambda x: S.select(x, x, 0.0),
+}
+_MAXIMUM = lambda x, y: S.select(x - y, x, y, False)      # noqa: E731
+_MINIMUM = lambda x, y: S.select(y - x, x, y, False)      # noqa: E731
+_BINARY = {
+    "mul": lambda x, y: x * y,
+    "xlogy": lambda x, y: x * S.log(y),
+    "xlog1py": lambda x, y: x * S.log1p(y),
+    "maximum": _MAXIMUM, "fmax": _MAXIMUM,
+    "minimum": _MINIMUM, "fmin": _MINIMUM,
+    "logaddexp": lambda x, y: _MAXIMUM(x, y) + S.log1p(S.exp(-S.absolute(x - y))),       # max(a, b) + log1p(exp(-|a - b|))
+}
+
+
+@_rule(*_UNARY)
+def _unary(c):
+    return c.U(c.args[0], _UNARY[c.base])
+
+
+@_rule(*_BINARY)
+def _binary(c):
+    return c.B(c.args[0], c.args[1], _BINARY[c.base])
+
+
+@_rule("div", "true_divide")
+def _div(c):
+    if c.kwargs.get("rounding_mode") is not None:
+        raise UnsupportedTorchOp("div with a rounding mode")
+    return c.B(c.args[0], c.args[1], lambda x, y: x / y)
+
+
+@_rule("pow")
+def _pow(c):
+    it, torch = c.it, c.it.torch
+    a0, a1 = c.args[0], c.args[1]
+    if it.is_const(a1) and (not isinstance(a1, torch.Tensor) or a1.numel() == 1):
+        e = _scalar(a1)
+        return c.U(a0, lambda x: _pow_const(x, e))
+    if it.is_const(a0) and (not isinstance(a0, torch.Tensor) or a0.numel() == 1):
+        b = _scalar(a0)
+        if b <= 0:
+            raise UnsupportedTorchOp("a non-positive constant to a traced power")
+        return c.U(a1, lambda y: S.exp(math.log(b) * y))
+    return c.B(a0, a1, _pow_traced)
+
+
+@_rule("sqrt", "exp", "log", "log1p", "sigmoid", "tanh", "expm1", "erf", "erfc", "sin", "cos", "atan", "lgamma", "digamma", "sign")
+def _unary_of_the_ir(c):
+    return c.U(c.args[0], lambda x: S._unary(c.base, x))
+
+
+@_rule("softplus")
+def _softplus(c):
+    beta = _scalar(c.arg(1, "beta", 1.0))
+    thr = _scalar(c.arg(2, "threshold", 20.0))
+    return c.U(c.args[0], lambda x: S.select(x * beta - thr, x, S.softplus(x * beta) * (1.0 / beta) if beta != 1.0 else S.softplus(x)))
+
+
+@_rule("log_sigmoid_forward")
+def _log_sigmoid_forward(c):
+    r = c.U(c.args[0], lambda x: -S.softplus(-x))
+    return (r, r)
+
+
+@_rule("clamp", "clamp_min", "clamp_max", "clip")
+def _clamp(c):
+    lo = c.arg(1, "min")
+    hi = c.arg(2, "max") if c.base in ("clamp", "clip") else None
+    if c.base == "clamp_max":
+        lo, hi = None, lo
+    r = c.it.sym(c.args[0])
+    if lo is not None:
+        r = c.B(r, lo, _MAXIMUM)
+    if hi is not None:
+        r = c.B(r, hi, _MINIMUM)
+    return r
+
+
+@_rule("gt", "lt", "ge", "le", "eq", "ne")
+def _compare(c):
+    return c.it.compare(c.args[0], c.args[1], c.base)
+
+
+@_rule("logical_not", "bitwise_not")
+def _not(c):
+    b = c.it.as_bool(c.args[0])
+    return _Bool(("not", b.tree), b.shape)
+
+
+@_rule("logical_and", "bitwise_and", "logical_or", "bitwise_or")
+def _and_or(c):
+    it, torch = c.it, c.it.torch
+    l, r = it.as_bool(c.args[0]), it.as_bool(c.args[1])
+    shape = tuple(torch.broadcast_shapes(l.shape, r.shape))
+    lt = l.tree if _numel(l.shape) == _numel(shape) else it.move(l, lambda t: torch.broadcast_to(t, shape)).tree
+    rt = r.tree if _numel(r.shape) == _numel(shape) else it.move(r, lambda t: torch.broadcast_to(t, shape)).tree
+    return _Bool(("and" if "and" in c.base else "or", lt, rt), shape)
+
+
+@_rule("where")
+def _where(c):
+    if len(c.args) != 3:
+        raise UnsupportedTorchOp("where(condition) without values")
+    return c.it.where(c.args[0], c.args[1], c.args[2])
+
+
+@_rule("masked_fill")
+def _masked_fill(c):
+    return c.it.where(c.args[1], c.args[2], c.args[0])
+
+
+# ---------------- reductions and products
+@_rule("sum")
+def _sum(c):
+    return c.it.sum(c.args[0], c.arg(1, "dim"), c.arg(2, "keepdim", False))
+
+
+@_rule("mean")
+def _mean(c):
+    r = c.it.sum(c.args[0], c.arg(1, "dim"), c.arg(2, "keepdim", False))
+    cnt = _numel(c.it.shape_of(c.args[0])) // max(_numel(r.shape), 1)
+    return _Sym(r.expr * (1.0 / cnt), r.shape)
+
+
+@_rule("var", "std")
+def _var(c):
+    # (sum of squared deviations from the mean) / (n - correction) over the given axes
+    it, a0 = c.it, c.args[0]
+    dims = c.arg(1, "dim")
+    corr = c.kwargs.get("correction", 1)
+    if isinstance(dims, bool):       # the overload var(x, unbiased)
+        corr, dims = (1 if dims else 0), None
+    corr = 1 if corr is None else corr
+    keep = c.kwargs.get("keepdim", False)
+    m_ = it.sum(a0, dims, True)
+    cnt = _numel(it.shape_of(a0)) // max(_numel(m_.shape), 1)
+    if cnt - corr <= 0:
+        raise UnsupportedTorchOp(f"{c.name} of {cnt} element(s) with correction {corr}")
+    dev = c.B(a0, _Sym(m_.expr * (1.0 / cnt), m_.shape), lambda x, y: x - y)
+    r = it.sum(_Sym(dev.expr * dev.expr, dev.shape), dims, keep)
+    e_ = r.expr * (1.0 / (cnt - corr))
+    return _Sym(S.sqrt(e_) if c.base == "std" else e_, r.shape)
+
+
+@_rule("linalg_vector_norm")
+def _vector_norm(c):
+    ord_ = c.arg(1, "ord", 2)
+    dims = c.arg(2, "dim")
+    keep = c.arg(3, "keepdim", False)
+    v_ = c.it.sym(c.args[0])
+    if ord_ in (2, 2.0):
+        r = c.it.sum(_Sym(v_.expr * v_.expr, v_.shape), dims, keep)
+        return _Sym(S.sqrt(r.expr), r.shape)
+    if ord_ in (1, 1.0):
+        return c.it.sum(_Sym(S.absolute(v_.expr), v_.shape), dims, keep)
+    raise UnsupportedTorchOp(f"{c.name} with ord = {ord_}")
+
+
+@_rule("amax", "amin", "max", "min", "logsumexp", "_softmax", "_log_softmax", "softmax", "log_softmax")
+def _max_reduction(c):
+    # reductions by the maximum — over ALL elements of the tensor (one chain's vector): the IR's `max` is dimension -> scalar
+    base, args = c.base, c.args
+    v_ = c.it.sym(args[0])
+    dims = c.arg(1, "dim")
+    if base in ("max", "min") and len(args) > 1:
+        raise UnsupportedTorchOp(f"{c.name} along an axis (values and indices)")
+    shp = v_.shape
+    nd = len(shp)
+    if dims is None or (isinstance(dims, (list, tuple)) and len(dims) == 0):
+        dims = list(range(nd))
+    if isinstance(dims, int):
+        dims = [dims]
+    dims = sorted({d_ % nd for d_ in dims}) if nd else []
+    if _numel(tuple(s_ for i_, s_ in enumerate(shp) if i_ not in dims)) != 1:
+        if len(dims) != 1 or shp[dims[0]] > 32:
+            raise UnsupportedTorchOp(f"{c.name} along an axis of more than 32 elements of a tensor with several rows")
+        return _max_along_axis(c, v_, dims[0])
+    return _max_over_all(c, v_, dims)
+
+
+def _keepdim_of(c) -> bool:
+    return bool(c.arg(2, "keepdim", False)) if c.base in ("amax", "amin", "logsumexp") else False
+
+
+def _max_along_axis(c, v_: _Sym, ax: int):
+    # along ONE short axis of a tensor with several rows (a multinomial logit: log_softmax of [observations, classes]): the
+    # maximum of every row as a chain of selects over the axis' slices, then the shifted sums as segment sums
+    it, base = c.it, c.base
+    keep = _keepdim_of(c)
+    sign = -1.0 if base in ("amin", "min") else 1.0
+    cols = [it.move(v_, lambda t, k_=k_: t.select(ax, k_).unsqueeze(ax)) for k_ in range(v_.shape[ax])]
+    m_ = cols[0] if sign > 0 else _Sym(-cols[0].expr, cols[0].shape)
+    for c_ in cols[1:]:
+        ce = c_.expr if sign > 0 else -c_.expr
+        m_ = _Sym(S.select(ce - m_.expr, ce, m_.expr, False), m_.shape)
+    squeeze = (lambda sv: sv if keep else it.move(sv, lambda t: t.squeeze(ax)))
+    if base in ("amax", "amin", "max", "min"):
+        return squeeze(_Sym(m_.expr if sign > 0 else -m_.expr, m_.shape))
+    sh = c.B(v_, m_, lambda x_, y_: x_ - y_)
+    ex = c.U(sh, S.exp)
+    tot = it.sum(ex, [ax], True)
+    if base == "logsumexp":
+        return squeeze(c.B(m_, c.U(tot, S.log), lambda x_, y_: x_ + y_))
+    if base in ("_softmax", "softmax"):
+        return c.B(ex, tot, lambda x_, y_: x_ / y_)
+    return c.B(sh, c.U(tot, S.log), lambda x_, y_: x_ - y_)
+
+
+def _max_over_all(c, v_: _Sym, dims: list):
+    base, shp = c.base, v_.shape
+    oshape = tuple(1 if i_ in dims else s_ for i_, s_ in enumerate(shp)) if _keepdim_of(c) else tuple(s_ for i_, s_ in enumerate(shp) if i_ not in dims)
+    e = v_.expr
+    if base in ("amax", "max"):
+        return _Sym(e.max() if e.dim is not None else e, oshape)
+    if base in ("amin", "min"):
+        return _Sym(-((-e).max()) if e.dim is not None else e, oshape)
+    if e.dim is None:      # all elements equal
+        n_ = float(_numel(shp))
+        return _Sym(e + math.log(n_), oshape) if base == "logsumexp" else _Sym(Expr.const(1.0 / n_) if "log" not in base else Expr.const(-math.log(n_)), shp)
+    m_ = e.max(constant=True)            # the shift: cancels exactly, no gradient through it
+    ex = S.exp(e - m_)
+    tot = ex.sum()
+    if base == "logsumexp":
+        return _Sym(m_ + S.log(tot), oshape)
+    if base in ("_softmax", "softmax"):
+        return _Sym(ex / tot, shp)
+    return _Sym((e - m_) - S.log(tot), shp)
+
+
+@_rule("cumsum")
+def _cumsum(c):
+    # a prefix sum along a short axis (ordered cut points: PyMC's `ordered` transform is a cumsum of exponentials): every output element
+    # sums the elements before it — a gather of the (i, j <= i) pairs and a segment sum back, n (n + 1) / 2 terms.  (A long axis of a
+    # traced value is a stage family's rule, asked before this one.)
+    it, torch = c.it, c.it.torch
+    v_ = it.sym(c.args[0])
+    shp = v_.shape
+    ax = c.arg(1, "dim") % max(len(shp), 1)
+    n_ax = shp[ax] if shp else 1
+    if v_.expr.dim is None:
+        ramp = torch.arange(1, n_ax + 1, dtype=torch.float64).reshape([n_ax if i_ == ax else 1 for i_ in range(len(shp))]).expand(shp)
+        return c.B(v_, ramp, lambda x_, y_: x_ * y_)
+    n_ = _numel(shp)
+    flat = torch.arange(n_, dtype=torch.int64).reshape(shp)
+    src, dst = [], []
+    for i_ in range(n_ax):
+        for j_ in range(i_ + 1):
+            src.append(flat.select(ax, j_).reshape(-1))
+            dst.append(flat.select(ax, i_).reshape(-1))
+    src, dst = torch.cat(src).numpy(), torch.cat(dst).numpy()
+    pairs = v_.expr[it.index(src, src.size, n_)]
+    return _Sym(S._segsum(pairs, it.index(dst, dst.size, n_)), shp)
+
+
+@_rule("dot", "vdot")
+def _dot(c):
+    return c.it.sum(c.B(c.args[0], c.args[1], lambda x, y: x * y))
+
+
+@_rule("linalg_solve_triangular")
+def _solve_triangular_constant(c):
+    # A X = B (left) or X A = B with a CONSTANT triangular A (the scale_tril of a MultivariateNormal): a product with A^-1.  (A traced A
+    # is a stage family's rule, asked before this one.)
+    torch, kwargs = c.it.torch, c.kwargs
+    A_, B_ = c.args[0], c.args[1]
+    eye = torch.eye(A_.shape[-1], dtype=A_.dtype)
+    Ainv = torch.linalg.solve_triangular(A_, eye.expand_as(A_).contiguous(), upper=bool(kwargs.get("upper", False)),
+                                         left=True, unitriangular=bool(kwargs.get("unitriangular", False)))
+    return c.it.matmul_like(Ainv, B_) if kwargs.get("left", True) else c.it.matmul_like(B_, Ainv)
+
+
+@_rule("mv", "mm", "matmul", "bmm")
+def _matmul(c):
+    return c.it.matmul_like(c.args[0], c.args[1])
+
+
+@_rule("addmm", "addmv")
+def _addmm(c):
+    beta, al = _scalar(c.kwargs.get("beta", 1)), c.alpha()
+    prod = c.it.matmul_like(c.args[1], c.args[2])
+    return c.B(c.args[0], prod, lambda x, y: (x if beta == 1 else beta * x) + (y if al == 1 else al * y))
+
+
+# ---------------- data movement
+# ("alias" was also listed with "clone" below: this listing came first, the other was dead)
+@_rule("view", "_unsafe_view", "reshape", "squeeze", "unsqueeze", "expand", "permute", "transpose", "t", "select", "slice", "narrow",
+       "flip", "diagonal", "alias", "flatten", "unflatten", "movedim", "swapaxes", "index_select", "roll", "repeat",
+       "split", "split_with_sizes", "unbind", "chunk", "as_strided", "expand_as", "view_as", "take")
+def _move(c):
+    if _any_traced(c.args[1:]) or _any_traced(list(c.kwargs.values())):
+        raise UnsupportedTorchOp(f"{c.name} with a traced index")
+    return c.it.move(c.args[0], lambda t: c.tgt(t, *c.args[1:], **c.kwargs))
+
+
+@_rule("tril", "triu")
+def _triangle(c):
+    raise UnsupportedTorchOp(c.base)
+
+
+@_rule("index")
+def _index(c):
+    idx = c.args[1]
+    if _any_traced(idx):
+        raise UnsupportedTorchOp("indexing with a traced index")
+    return c.it.move(c.args[0], lambda t: c.tgt(t, idx))
+
+
+@_rule("gather")
+def _gather(c):
+    if _any_traced(c.args[1:]):
+        raise UnsupportedTorchOp("gather with a traced index")
+    return c.it.move(c.args[0], lambda t: c.tgt(t, *c.args[1:], **c.kwargs))
+
+
+# (of a partitioned x, "clone", "contiguous", "detach", "lift_fresh_copy" and "_to_copy" are `_x_rule`'s, which is tried first)
+@_rule("clone", "contiguous", "detach", "lift_fresh_copy", "lift_fresh", "positive", "_to_copy", "to", "type_as", "double", "float")
+def _convert(c):
+    a0, dt = c.args[0], c.kwargs.get("dtype")
+    if isinstance(a0, _Bool) and (dt is None or dt == c.it.torch.bool):
+        return a0
+    if dt is not None and not dt.is_floating_point:
+        raise UnsupportedTorchOp(f"a traced value converted to {dt}")
+    return c.it.sym(a0)
+
+
+@_rule("cat", "concat", "concatenate")
+def _cat(c):
+    return c.it.cat(list(c.args[0]), c.arg(1, "dim", 0))
+
+
+@_rule("stack")
+def _stack(c):
+    it = c.it
+    d_ = c.arg(1, "dim", 0)
+    parts = [it.move(p, lambda t: t.unsqueeze(d_ if d_ >= 0 else d_ + t.dim() + 1)) if not it.is_const(p) else p.unsqueeze(d_) for p in c.args[0]]
+    return it.cat(parts, d_)
+
+
+@_rule("zeros_like", "ones_like", "full_like", "empty_like", "new_zeros", "new_ones", "new_full", "new_empty")
+def _constant_like(c):
+    proxy = c.it.torch.zeros(c.it.shape_of(c.args[0]), dtype=c.it.torch.float64)
+    return c.tgt(proxy, *c.args[1:], **{k: v for k, v in c.kwargs.items() if k not in ("device", "pin_memory", "layout")})
+
+
+# ---------------- scatter forms
+def _flat_elements(it: _Interp, shape):
+    """the flat element numbers of a tensor of ``shape``, as a tensor of that shape: what a view or an index of it is a map of"""
+    return it.torch.arange(_numel(shape), dtype=it.torch.int64).reshape(shape)
+
+
+def _onto(it: _Interp, src, tmap) -> tuple[_Sym, np.ndarray]:
+    """``src`` broadcast to the elements ``tmap`` names, and their flat numbers"""
+    shape = tuple(tmap.shape)
+    return _Sym(it.broadcast(it.sym(src), shape), shape), tmap.reshape(-1).numpy()
+
+
+@_rule("index_add")
+def _index_add(c):
+    it, args = c.it, c.args
+    if _any_traced([args[1], args[2]]):
+        raise UnsupportedTorchOp("index_add with a traced index")
+    tmap = _flat_elements(it, it.shape_of(args[0])).index_select(args[1], args[2])
+    src = it.sym(args[3])
+    al = c.alpha()
+    if al != 1:
+        src = _Sym(src.expr * al, src.shape)
+    return it.scatter_add(args[0], *_onto(it, src, tmap))
+
+
+@_rule("scatter_add")
+def _scatter_add(c):
+    it, args = c.it, c.args
+    torch = it.torch
+    if _any_traced([args[1], args[2]]):
+        raise UnsupportedTorchOp("scatter_add with a traced index")
+    base_shape = it.shape_of(args[0])
+    index = args[2]
+    # element (i, j, ...) of src (restricted to index's shape) goes to base[..., index[i, j, ...], ...]
+    src = it.move(it.sym(args[3]), lambda t: t[tuple(slice(0, s) for s in index.shape)])
+    coords = torch.meshgrid(*[torch.arange(s) for s in index.shape], indexing="ij") if index.dim() else ()
+    coords = list(coords)
+    if index.dim():
+        coords[args[1] % index.dim()] = index
+        strides = torch.tensor([int(np.prod(base_shape[i + 1:], dtype=np.int64)) for i in range(len(base_shape))])
+        tflat = sum(c_ * s for c_, s in zip(coords, strides)).reshape(-1).numpy()
+    else:
+        tflat = np.zeros(1, dtype=np.int64)
+    return it.scatter_add(args[0], src, tflat)
+
+
+@_rule("copy")
+def _copy(c):
+    src = c.it.sym(c.args[1])
+    shp = c.it.shape_of(c.args[0])
+    return _Sym(c.it.broadcast(src, shp), shp)
+
+
+@_rule("slice_scatter", "select_scatter", "diagonal_scatter")
+def _view_scatter(c):
+    it, aten = c.it, c.it.torch.ops.aten
+    view = {"slice_scatter": aten.slice.Tensor, "select_scatter": aten.select.int, "diagonal_scatter": aten.diagonal.default}[c.base]
+    tmap = view(_flat_elements(it, it.shape_of(c.args[0])), *c.args[2:], **c.kwargs)
+    return _scatter_replace(it, c.args[0], *_onto(it, c.args[1], tmap))
+
+
+@_rule("index_put")
+def _index_put(c):
+    it, idx = c.it, c.args[1]
+    if _any_traced(idx):
+        raise UnsupportedTorchOp("index_put with a traced index")
+    tmap = it.torch.ops.aten.index.Tensor(_flat_elements(it, it.shape_of(c.args[0])), idx)
+    src, flat = _onto(it, c.args[2], tmap)
+    return it.scatter_add(c.args[0], src, flat) if c.arg(3, "accumulate", False) else _scatter_replace(it, c.args[0], src, flat)
+
+
+# ------------------------------------------------------------------------------------------------------------------- the graph walk
 def _run(gm, it: _Interp, x_shape, data_values: dict[str, Any]):
     import torch
 
-    aten = torch.ops.aten
     env: dict[Any, Any] = {}
     placeholders = [n for n in gm.graph.nodes if n.op == "placeholder"]
     n_ops = 0
@@ -976,29 +1087,6 @@ def _run(gm, it: _Interp, x_shape, data_values: dict[str, Any]):
         if isinstance(a, (list, tuple)):
             return type(a)(val(v) for v in a)
         return a
-
-    def to_host(v):
-        if isinstance(v, torch.Tensor):
-            return v.detach().cpu()
-        if isinstance(v, (list, tuple)):
-            return type(v)(to_host(t) for t in v)
-        return v
-
-    def const_call(node, args, kwargs):
-        # (constants live on the host whatever device the function was traced on)
-        kwargs = {k: (torch.device("cpu") if k == "device" else v) for k, v in kwargs.items()}
-        return to_host(node.target(*args, **kwargs))
-
-    def any_traced(v) -> bool:
-        if isinstance(v, (list, tuple)):
-            return any(any_traced(t) for t in v)
-        return isinstance(v, (_Sym, _Bool, _X))
-
-    def x_piece(xv: _X, lo: int, hi: int, scalar: bool, out_shape):
-        if it.whole:
-            return None
-        sv = it.piece(lo, hi, scalar)
-        return _Sym(sv.expr, out_shape)
 
     for node in gm.graph.nodes:
         if node.op == "placeholder":
@@ -1014,8 +1102,7 @@ def _run(gm, it: _Interp, x_shape, data_values: dict[str, Any]):
                     it._alive.append(t)
             continue
         if node.op == "get_attr":
-            t = getattr(gm, node.target)
-            env[node] = to_host(t)
+            env[node] = _to_host(getattr(gm, node.target))
             continue
         if node.op == "output":
             out = val(node.args[0])
@@ -1032,428 +1119,17 @@ def _run(gm, it: _Interp, x_shape, data_values: dict[str, Any]):
         if tgt is operator.getitem:
             env[node] = args[0][args[1]]
             continue
-        if not any_traced(args) and not any_traced(list(kwargs.values())):
-            env[node] = const_call(node, args, kwargs)               # constants only: evaluated now
+        if not _any_traced(args) and not _any_traced(list(kwargs.values())):
+            # constants only: evaluated now (they live on the host whatever device the function was traced on)
+            env[node] = _to_host(tgt(*args, **{k: (torch.device("cpu") if k == "device" else v) for k, v in kwargs.items()}))
             continue
         name = tgt.__name__ if hasattr(tgt, "__name__") else str(tgt)
         pkt = getattr(tgt, "overloadpacket", None)
         base = pkt.__name__ if pkt is not None else name
         if base.endswith("_copy") and base not in ("_to_copy", "lift_fresh_copy"):
             base = base[:-5]                      # (functionalised views: slice_copy, select_copy, view_copy, expand_copy ... move data like their views)
-        a0 = args[0] if args else None
-
-        # ---------------- the position vector: pieces become parameters
-        if isinstance(a0, _X) and not it.whole:
-            D = it.n_dim
-            shp = a0.shape
-            ax = [i for i, s in enumerate(shp) if s != 1]
-            ax = ax[0] if ax else len(shp) - 1
-            if base == "select":
-                d_, idx = args[1] % len(shp), args[2]
-                if d_ == ax and D > 0:
-                    idx = idx % D
-                    env[node] = x_piece(a0, idx, idx + 1, True, tuple(s for i, s in enumerate(shp) if i != d_))
-                    continue
-                if shp[d_] == 1:
-                    env[node] = _X(tuple(s for i, s in enumerate(shp) if i != d_))
-                    continue
-            elif base == "slice":
-                d_ = (args[1] if len(args) > 1 else 0) % len(shp)
-                lo = args[2] if len(args) > 2 and args[2] is not None else 0
-                hi = args[3] if len(args) > 3 and args[3] is not None else shp[d_]
-                step = args[4] if len(args) > 4 else 1
-                lo, hi, _ = slice(lo, hi, step).indices(shp[d_])
-                if d_ == ax and step == 1:
-                    if lo == 0 and hi == D:
-                        env[node] = a0
-                    elif hi > lo:
-                        env[node] = x_piece(a0, lo, hi, False, tuple((hi - lo) if i == d_ else s for i, s in enumerate(shp)))
-                    else:
-                        raise UnsupportedTorchOp("an empty slice of x")
-                    continue
-                if d_ != ax and lo == 0 and hi == shp[d_] and step == 1:
-                    env[node] = a0
-                    continue
-            elif base in ("split", "split_with_sizes", "unbind", "chunk"):
-                probe = tgt(torch.arange(D, dtype=torch.int64).reshape(shp), *args[1:], **kwargs)
-                outs = []
-                ok = True
-                for p in probe:
-                    f = p.reshape(-1)
-                    if f.numel() == 0 or not torch.equal(f, torch.arange(int(f[0]), int(f[0]) + f.numel())):
-                        ok = False
-                        break
-                    outs.append((int(f[0]), int(f[0]) + f.numel(), tuple(p.shape)))
-                if ok:
-                    env[node] = [x_piece(a0, lo, hi, _numel(s) == 1 and base == "unbind", s) for lo, hi, s in outs]
-                    continue
-            elif base in ("view", "_unsafe_view", "reshape", "squeeze", "unsqueeze", "alias", "detach", "clone", "contiguous", "_to_copy", "lift_fresh_copy", "flatten", "expand"):
-                probe = tgt(torch.zeros(shp, dtype=torch.float64), *args[1:], **kwargs)
-                if probe.numel() == D and sum(1 for s in probe.shape if s != 1) <= 1:
-                    env[node] = _X(tuple(probe.shape))
-                    continue
-            raise _NeedWholeVector(f"x is used by {name}")
-
-        # ---------------- element-wise arithmetic
-        B = it.binary
-        U = it.unary
-
-        def alpha_of():
-            return _scalar(kwargs.get("alpha", 1))
-
-        if base == "add":
-            al = alpha_of()
-            env[node] = B(args[0], args[1], lambda x, y: x + (y if al == 1 else al * y))
-        elif base == "sub":
-            al = alpha_of()
-            env[node] = B(args[0], args[1], lambda x, y: x - (y if al == 1 else al * y))
-        elif base == "rsub":
-            al = alpha_of()
-            env[node] = B(args[0], args[1], lambda x, y: y - (x if al == 1 else al * x))
-        elif base == "mul":
-            env[node] = B(args[0], args[1], lambda x, y: x * y)
-        elif base in ("div", "true_divide"):
-            if kwargs.get("rounding_mode") is not None:
-                raise UnsupportedTorchOp("div with a rounding mode")
-            env[node] = B(args[0], args[1], lambda x, y: x / y)
-        elif base == "neg":
-            env[node] = U(a0, lambda x: -x)
-        elif base == "reciprocal":
-            env[node] = U(a0, lambda x: 1.0 / x)
-        elif base == "square":
-            env[node] = U(a0, lambda x: x * x)
-        elif base == "pow":
-            if it.is_const(args[1]) and (not isinstance(args[1], torch.Tensor) or args[1].numel() == 1):
-                c = _scalar(args[1])
-                env[node] = U(a0, lambda x: _pow_const(x, c))
-            elif it.is_const(a0) and (not isinstance(a0, torch.Tensor) or a0.numel() == 1):
-                c = _scalar(a0)
-                if c <= 0:
-                    raise UnsupportedTorchOp("a non-positive constant to a traced power")
-                env[node] = U(args[1], lambda y: S.exp(math.log(c) * y))
-            else:
-                env[node] = B(args[0], args[1], _pow_traced)
-        elif base in ("sqrt", "exp", "log", "log1p", "sigmoid", "tanh", "expm1", "erf", "erfc", "sin", "cos", "atan", "lgamma", "digamma", "sign"):
-            env[node] = U(a0, lambda x: S._unary(base, x))
-        elif base == "abs":
-            env[node] = U(a0, S.absolute)
-        elif base == "rsqrt":
-            env[node] = U(a0, lambda x: 1.0 / S.sqrt(x))
-        elif base == "log2":
-            env[node] = U(a0, lambda x: S.log(x) * (1.0 / math.log(2.0)))
-        elif base == "log10":
-            env[node] = U(a0, lambda x: S.log(x) * (1.0 / math.log(10.0)))
-        elif base == "exp2":
-            env[node] = U(a0, lambda x: S.exp(x * math.log(2.0)))
-        elif base == "softplus":
-            beta = _scalar(args[1] if len(args) > 1 else kwargs.get("beta", 1.0))
-            thr = _scalar(args[2] if len(args) > 2 else kwargs.get("threshold", 20.0))
-            env[node] = U(a0, lambda x: S.select(x * beta - thr, x, S.softplus(x * beta) * (1.0 / beta) if beta != 1.0 else S.softplus(x)))
-        elif base == "log_sigmoid_forward":
-            r = U(a0, lambda x: -S.softplus(-x))
-            env[node] = (r, r)
-        elif base == "logit":
-            env[node] = U(a0, lambda x: S.log(x) - S.log1p(-x))
-        elif base == "xlogy":
-            env[node] = B(args[0], args[1], lambda x, y: x * S.log(y))
-        elif base == "xlog1py":
-            env[node] = B(args[0], args[1], lambda x, y: x * S.log1p(y))
-        elif base == "relu":
-            env[node] = U(a0, lambda x: S.select(x, x, 0.0))
-        elif base in ("maximum", "fmax"):
-            env[node] = B(args[0], args[1], lambda x, y: S.select(x - y, x, y, False))
-        elif base in ("minimum", "fmin"):
-            env[node] = B(args[0], args[1], lambda x, y: S.select(y - x, x, y, False))
-        elif base in ("clamp", "clamp_min", "clamp_max", "clip"):
-            lo = args[1] if len(args) > 1 else kwargs.get("min")
-            hi = (args[2] if len(args) > 2 else kwargs.get("max")) if base in ("clamp", "clip") else None
-            if base == "clamp_max":
-                lo, hi = None, lo
-            r = it.sym(a0)
-            if lo is not None:
-                r = B(r, lo, lambda x, y: S.select(x - y, x, y, False))
-            if hi is not None:
-                r = B(r, hi, lambda x, y: S.select(y - x, x, y, False))
-            env[node] = r
-        elif base in ("gt", "lt", "ge", "le", "eq", "ne"):
-            env[node] = it.compare(args[0], args[1], base)
-        elif base == "logaddexp":
-            # max(a, b) + log1p(exp(-|a - b|))
-            env[node] = B(args[0], args[1], lambda x, y: S.select(x - y, x, y, False) + S.log1p(S.exp(-S.absolute(x - y))))
-        elif base in ("logical_not", "bitwise_not"):
-            b_ = it.as_bool(a0)
-            env[node] = _Bool(("not", b_.tree), b_.shape)
-        elif base in ("logical_and", "bitwise_and", "logical_or", "bitwise_or"):
-            l, r = it.as_bool(args[0]), it.as_bool(args[1])
-            shape = tuple(torch.broadcast_shapes(l.shape, r.shape))
-            lt = l.tree if _numel(l.shape) == _numel(shape) else it.move(l, lambda t: torch.broadcast_to(t, shape)).tree
-            rt = r.tree if _numel(r.shape) == _numel(shape) else it.move(r, lambda t: torch.broadcast_to(t, shape)).tree
-            env[node] = _Bool(("and" if "and" in base else "or", lt, rt), shape)
-        elif base == "where":
-            if len(args) != 3:
-                raise UnsupportedTorchOp("where(condition) without values")
-            env[node] = it.where(args[0], args[1], args[2])
-        elif base == "masked_fill":
-            env[node] = it.where(args[1], args[2], args[0])
-        # ---------------- reductions and products
-        elif base == "sum":
-            env[node] = it.sum(a0, args[1] if len(args) > 1 else kwargs.get("dim"), args[2] if len(args) > 2 else kwargs.get("keepdim", False))
-        elif base == "mean":
-            dims = args[1] if len(args) > 1 else kwargs.get("dim")
-            r = it.sum(a0, dims, args[2] if len(args) > 2 else kwargs.get("keepdim", False))
-            cnt = _numel(it.shape_of(a0)) // max(_numel(r.shape), 1)
-            env[node] = _Sym(r.expr * (1.0 / cnt), r.shape)
-        elif base in ("var", "std"):
-            # (sum of squared deviations from the mean) / (n - correction) over the given axes
-            dims = args[1] if len(args) > 1 else kwargs.get("dim")
-            corr = kwargs.get("correction", 1)
-            if isinstance(dims, bool):       # the overload var(x, unbiased)
-                corr, dims = (1 if dims else 0), None
-            corr = 1 if corr is None else corr
-            keep = kwargs.get("keepdim", False)
-            m_ = it.sum(a0, dims, True)
-            cnt = _numel(it.shape_of(a0)) // max(_numel(m_.shape), 1)
-            if cnt - corr <= 0:
-                raise UnsupportedTorchOp(f"{name} of {cnt} element(s) with correction {corr}")
-            dev = B(a0, _Sym(m_.expr * (1.0 / cnt), m_.shape), lambda x, y: x - y)
-            r = it.sum(_Sym(dev.expr * dev.expr, dev.shape), dims, keep)
-            e_ = r.expr * (1.0 / (cnt - corr))
-            env[node] = _Sym(S.sqrt(e_) if base == "std" else e_, r.shape)
-        elif base == "linalg_vector_norm":
-            ord_ = args[1] if len(args) > 1 else kwargs.get("ord", 2)
-            dims = args[2] if len(args) > 2 else kwargs.get("dim")
-            keep = args[3] if len(args) > 3 else kwargs.get("keepdim", False)
-            v_ = it.sym(a0)
-            if ord_ in (2, 2.0):
-                r = it.sum(_Sym(v_.expr * v_.expr, v_.shape), dims, keep)
-                env[node] = _Sym(S.sqrt(r.expr), r.shape)
-            elif ord_ in (1, 1.0):
-                r = it.sum(_Sym(S.absolute(v_.expr), v_.shape), dims, keep)
-                env[node] = r
-            else:
-                raise UnsupportedTorchOp(f"{name} with ord = {ord_}")
-        elif base in ("amax", "amin", "max", "min", "logsumexp", "_softmax", "_log_softmax", "softmax", "log_softmax"):
-            # reductions by the maximum — over ALL elements of the tensor (one chain's vector): the IR's `max` is dimension -> scalar
-            v_ = it.sym(a0)
-            dims = args[1] if len(args) > 1 else kwargs.get("dim")
-            if base in ("max", "min") and len(args) > 1:
-                raise UnsupportedTorchOp(f"{name} along an axis (values and indices)")
-            shp = v_.shape
-            nd = len(shp)
-            if dims is None or (isinstance(dims, (list, tuple)) and len(dims) == 0):
-                dims = list(range(nd))
-            if isinstance(dims, int):
-                dims = [dims]
-            dims = sorted({d_ % nd for d_ in dims}) if nd else []
-            if _numel(tuple(s_ for i_, s_ in enumerate(shp) if i_ not in dims)) != 1:
-                # along ONE short axis of a tensor with several rows (a multinomial logit: log_softmax of [observations, classes]): the
-                # maximum of every row as a chain of selects over the axis' slices, then the shifted sums as segment sums
-                if len(dims) != 1 or shp[dims[0]] > 32:
-                    raise UnsupportedTorchOp(f"{name} along an axis of more than 32 elements of a tensor with several rows")
-                ax = dims[0]
-                keep = bool(args[2] if len(args) > 2 else kwargs.get("keepdim", False)) if base in ("amax", "amin", "logsumexp") else False
-                sign = -1.0 if base in ("amin", "min") else 1.0
-                cols = [it.move(v_, lambda t, k_=k_: t.select(ax, k_).unsqueeze(ax)) for k_ in range(shp[ax])]
-                m_ = cols[0] if sign > 0 else _Sym(-cols[0].expr, cols[0].shape)
-                for c_ in cols[1:]:
-                    ce = c_.expr if sign > 0 else -c_.expr
-                    m_ = _Sym(S.select(ce - m_.expr, ce, m_.expr, False), m_.shape)
-                squeeze = (lambda sv: sv if keep else it.move(sv, lambda t: t.squeeze(ax)))
-                if base in ("amax", "amin", "max", "min"):
-                    env[node] = squeeze(_Sym(m_.expr if sign > 0 else -m_.expr, m_.shape))
-                    continue
-                sh = B(v_, m_, lambda x_, y_: x_ - y_)
-                ex = U(sh, S.exp)
-                tot = it.sum(ex, [ax], True)
-                if base == "logsumexp":
-                    env[node] = squeeze(B(m_, U(tot, S.log), lambda x_, y_: x_ + y_))
-                elif base in ("_softmax", "softmax"):
-                    env[node] = B(ex, tot, lambda x_, y_: x_ / y_)
-                else:
-                    env[node] = B(sh, U(tot, S.log), lambda x_, y_: x_ - y_)
-                continue
-            keep = bool(args[2] if len(args) > 2 else kwargs.get("keepdim", False)) if base in ("amax", "amin", "logsumexp") else False
-            oshape = tuple(1 if i_ in dims else s_ for i_, s_ in enumerate(shp)) if keep else tuple(s_ for i_, s_ in enumerate(shp) if i_ not in dims)
-            e = v_.expr
-            if base in ("amax", "max"):
-                env[node] = _Sym(e.max() if e.dim is not None else e, oshape)
-            elif base in ("amin", "min"):
-                env[node] = _Sym(-((-e).max()) if e.dim is not None else e, oshape)
-            elif e.dim is None:      # all elements equal
-                n_ = float(_numel(shp))
-                env[node] = _Sym(e + math.log(n_), oshape) if base == "logsumexp" else _Sym(Expr.const(1.0 / n_) if "log" not in base else Expr.const(-math.log(n_)), shp)
-            else:
-                m_ = e.max(constant=True)            # the shift: cancels exactly, no gradient through it
-                ex = S.exp(e - m_)
-                tot = ex.sum()
-                if base == "logsumexp":
-                    env[node] = _Sym(m_ + S.log(tot), oshape)
-                elif base in ("_softmax", "softmax"):
-                    env[node] = _Sym(ex / tot, shp)
-                else:
-                    env[node] = _Sym((e - m_) - S.log(tot), shp)
-        elif base in ("cumsum", "logcumsumexp") and base == "cumsum":
-            # a prefix sum along a short axis (ordered cut points: PyMC's `ordered` transform is a cumsum of exponentials): every output element
-            # sums the elements before it — a gather of the (i, j <= i) pairs and a segment sum back, n (n + 1) / 2 terms
-            v_ = it.sym(a0)
-            shp = v_.shape
-            ax = (args[1] if len(args) > 1 else kwargs.get("dim")) % max(len(shp), 1)
-            n_ax = shp[ax] if shp else 1
-            if n_ax > 64 and v_.expr.dim is not None:
-                # a long axis: the IR's scan stage with a = 1 (csrc/chain_scan.h), the axis moved last and the others as rows
-                env[node] = _scan_traced(it, 1.0, v_, 0.0, ax)
-            elif v_.expr.dim is None:
-                ramp = torch.arange(1, n_ax + 1, dtype=torch.float64).reshape([n_ax if i_ == ax else 1 for i_ in range(len(shp))]).expand(shp)
-                env[node] = B(v_, ramp, lambda x_, y_: x_ * y_)
-            else:
-                n_ = _numel(shp)
-                flat = torch.arange(n_, dtype=torch.int64).reshape(shp)
-                src, dst = [], []
-                for i_ in range(n_ax):
-                    for j_ in range(i_ + 1):
-                        src.append(flat.select(ax, j_).reshape(-1))
-                        dst.append(flat.select(ax, i_).reshape(-1))
-                src, dst = torch.cat(src).numpy(), torch.cat(dst).numpy()
-                pairs = v_.expr[it.index(src, src.size, n_)]
-                env[node] = _Sym(S._segsum(pairs, it.index(dst, dst.size, n_)), shp)
-        elif base == "linear_recurrence":
-            # nutpie_amd::linear_recurrence (this module's custom op; time is the last axis): the IR's scan stage
-            env[node] = _scan_traced(it, args[0], it.sym(args[1]), args[2], len(it.shape_of(args[1])) - 1)
-        elif base == "kalman_marginal":
-            # nutpie_amd::kalman_marginal (this module's custom op): the IR's Kalman filter stage
-            env[node] = _kalman_traced(it, *args[:8])
-        elif base == "hmm_marginal":
-            # nutpie_amd::hmm_marginal (this module's custom op): the IR's HMM stage
-            env[node] = _hmm_traced(it, args[0], args[1], args[2])
-        elif base == "dot" or base == "vdot":
-            env[node] = it.sum(B(args[0], args[1], lambda x, y: x * y))
-        elif base in ("linalg_cholesky_ex", "linalg_cholesky", "cholesky"):
-            # a traced matrix: the IR's Cholesky stage (one chain's K x K matrix; csrc/chain_linalg.h)
-            upper = bool(args[1] if len(args) > 1 else kwargs.get("upper", False))
-            Lsym = _cholesky(it, a0)
-            if upper:
-                Lsym = it.move(Lsym, lambda t: t.transpose(-1, -2))
-            if base == "linalg_cholesky_ex":
-                # (info: 0 — a matrix that is not positive definite makes the density NaN instead of raising)
-                env[node] = (Lsym, torch.zeros(Lsym.shape[:-2], dtype=torch.int32))
-            else:
-                env[node] = Lsym
-        elif base == "linalg_solve_triangular" and not it.is_const(args[0]):
-            # a traced triangular matrix: the IR's triangular solve (lower, left) — other forms through transposes and reversals
-            if bool(kwargs.get("unitriangular", False)):
-                raise UnsupportedTorchOp(f"{name} with unitriangular=True and a traced matrix")
-            env[node] = _solve_triangular(it, args[0], args[1], bool(kwargs.get("upper", False)), bool(kwargs.get("left", True)))
-        elif base == "linalg_solve_triangular":
-            # A X = B (left) or X A = B with a CONSTANT triangular A (the scale_tril of a MultivariateNormal): a product with A^-1
-            A_, B_ = args[0], args[1]
-            eye = torch.eye(A_.shape[-1], dtype=A_.dtype)
-            Ainv = torch.linalg.solve_triangular(A_, eye.expand_as(A_).contiguous(), upper=bool(kwargs.get("upper", False)),
-                                                 left=True, unitriangular=bool(kwargs.get("unitriangular", False)))
-            env[node] = it.matmul_like(Ainv, B_) if kwargs.get("left", True) else it.matmul_like(B_, Ainv)
-        elif base in ("mv", "mm", "matmul", "bmm"):
-            env[node] = it.matmul_like(args[0], args[1])
-        elif base == "addmm" or base == "addmv":
-            beta, al = _scalar(kwargs.get("beta", 1)), _scalar(kwargs.get("alpha", 1))
-            prod = it.matmul_like(args[1], args[2])
-            env[node] = B(args[0], prod, lambda x, y: (x if beta == 1 else beta * x) + (y if al == 1 else al * y))
-        # ---------------- data movement
-        elif base in ("view", "_unsafe_view", "reshape", "squeeze", "unsqueeze", "expand", "permute", "transpose", "t", "select", "slice", "narrow",
-                      "flip", "diagonal", "alias", "flatten", "unflatten", "movedim", "swapaxes", "index_select", "roll", "repeat", "tril", "triu",
-                      "split", "split_with_sizes", "unbind", "chunk", "as_strided", "expand_as", "view_as", "take"):
-            if base in ("tril", "triu"):
-                raise UnsupportedTorchOp(base)
-            if any_traced(args[1:]) or any_traced(list(kwargs.values())):
-                raise UnsupportedTorchOp(f"{name} with a traced index")
-            env[node] = it.move(a0, lambda t: tgt(t, *args[1:], **kwargs))
-        elif base == "index":
-            idx = args[1]
-            if any_traced(idx):
-                raise UnsupportedTorchOp("indexing with a traced index")
-            if any(isinstance(i_, torch.Tensor) and i_.dtype == torch.bool for i_ in idx if i_ is not None):
-                pass
-            env[node] = it.move(a0, lambda t: tgt(t, idx))
-        elif base == "gather":
-            if any_traced(args[1:]):
-                raise UnsupportedTorchOp("gather with a traced index")
-            env[node] = it.move(a0, lambda t: tgt(t, *args[1:], **kwargs))
-        elif base in ("clone", "contiguous", "detach", "lift_fresh_copy", "lift_fresh", "alias", "positive", "_to_copy", "to", "type_as", "double", "float"):
-            dt = kwargs.get("dtype")
-            if isinstance(a0, _Bool) and (dt is None or dt == torch.bool):
-                env[node] = a0
-            elif dt is not None and not dt.is_floating_point:
-                raise UnsupportedTorchOp(f"a traced value converted to {dt}")
-            else:
-                env[node] = it.sym(a0)
-        elif base == "cat" or base == "concat" or base == "concatenate":
-            env[node] = it.cat(list(args[0]), args[1] if len(args) > 1 else kwargs.get("dim", 0))
-        elif base == "stack":
-            d_ = args[1] if len(args) > 1 else kwargs.get("dim", 0)
-            parts = [it.move(p, lambda t: t.unsqueeze(d_ if d_ >= 0 else d_ + t.dim() + 1)) if not it.is_const(p) else p.unsqueeze(d_) for p in args[0]]
-            env[node] = it.cat(parts, d_)
-        elif base in ("zeros_like", "ones_like", "full_like", "empty_like", "new_zeros", "new_ones", "new_full", "new_empty"):
-            shp = it.shape_of(a0)
-            proxy = torch.zeros(shp, dtype=torch.float64)
-            env[node] = tgt(proxy, *args[1:], **{k: v for k, v in kwargs.items() if k not in ("device", "pin_memory", "layout")})
-        elif base == "index_add":
-            if any_traced([args[1], args[2]]):
-                raise UnsupportedTorchOp("index_add with a traced index")
-            base_shape = it.shape_of(args[0])
-            tmap = torch.arange(_numel(base_shape), dtype=torch.int64).reshape(base_shape).index_select(args[1], args[2])
-            src = it.sym(args[3])
-            al = alpha_of()
-            if al != 1:
-                src = _Sym(src.expr * al, src.shape)
-            srcb = _Sym(it.broadcast(src, tuple(tmap.shape)), tuple(tmap.shape))
-            env[node] = it.scatter_add(args[0], srcb, tmap.reshape(-1).numpy())
-        elif base == "scatter_add":
-            if any_traced([args[1], args[2]]):
-                raise UnsupportedTorchOp("scatter_add with a traced index")
-            base_shape = it.shape_of(args[0])
-            index = args[2]
-            tmap = torch.arange(_numel(base_shape), dtype=torch.int64).reshape(base_shape).gather(args[1], index)
-            # element (i, j, ...) of src (restricted to index's shape) goes to base[..., index[i, j, ...], ...]
-            src = it.move(it.sym(args[3]), lambda t: t[tuple(slice(0, s) for s in index.shape)])
-            coords = torch.meshgrid(*[torch.arange(s) for s in index.shape], indexing="ij") if index.dim() else ()
-            coords = list(coords)
-            if index.dim():
-                coords[args[1] % index.dim()] = index
-                strides = torch.tensor([int(np.prod(base_shape[i + 1:], dtype=np.int64)) for i in range(len(base_shape))])
-                tflat = sum(c * s for c, s in zip(coords, strides)).reshape(-1).numpy()
-            else:
-                tflat = np.zeros(1, dtype=np.int64)
-            del tmap
-            env[node] = it.scatter_add(args[0], src, tflat)
-        elif base == "copy":
-            src = it.sym(args[1])
-            shp = it.shape_of(args[0])
-            env[node] = _Sym(it.broadcast(src, shp), shp)
-        elif base in ("slice_scatter", "select_scatter", "diagonal_scatter"):
-            base_shape = it.shape_of(args[0])
-            view = {"slice_scatter": torch.ops.aten.slice.Tensor, "select_scatter": torch.ops.aten.select.int, "diagonal_scatter": torch.ops.aten.diagonal.default}[base]
-            tmap = view(torch.arange(_numel(base_shape), dtype=torch.int64).reshape(base_shape), *args[2:], **kwargs)
-            src = it.sym(args[1])
-            srcb = _Sym(it.broadcast(src, tuple(tmap.shape)), tuple(tmap.shape))
-            env[node] = _scatter_replace(it, args[0], srcb, tmap.reshape(-1).numpy())
-        elif base == "index_put" and not (args[3] if len(args) > 3 else kwargs.get("accumulate", False)):
-            idx = args[1]
-            if any_traced(idx):
-                raise UnsupportedTorchOp("index_put with a traced index")
-            base_shape = it.shape_of(args[0])
-            tmap = torch.ops.aten.index.Tensor(torch.arange(_numel(base_shape), dtype=torch.int64).reshape(base_shape), idx)
-            src = it.sym(args[2])
-            srcb = _Sym(it.broadcast(src, tuple(tmap.shape)), tuple(tmap.shape))
-            env[node] = _scatter_replace(it, args[0], srcb, tmap.reshape(-1).numpy())
-        elif base == "index_put":
-            idx = args[1]
-            if any_traced(idx):
-                raise UnsupportedTorchOp("index_put with a traced index")
-            base_shape = it.shape_of(args[0])
-            tmap = torch.ops.aten.index.Tensor(torch.arange(_numel(base_shape), dtype=torch.int64).reshape(base_shape), idx)
-            src = it.sym(args[2])
-            srcb = _Sym(it.broadcast(src, tuple(tmap.shape)), tuple(tmap.shape))
-            env[node] = it.scatter_add(args[0], srcb, tmap.reshape(-1).numpy())
-        else:
-            raise UnsupportedTorchOp(f"{name} (no counterpart in the expression IR)")
+        c = _Ctx(it, node, tgt, name, base, args, kwargs)
+        env[node] = _x_rule(c) if args and isinstance(args[0], _X) and not it.whole else _lower(c)
     raise UnsupportedTorchOp("the traced graph has no output")
 
 
