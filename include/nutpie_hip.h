@@ -360,6 +360,10 @@ int nphip_test_rowpool(int threads, uint64_t rows, int batches, int use, uint64_
  * choose_geometry) and whether the table of kernel families (csrc/kernel_families.h) has that instantiation */
 int nphip_test_choose_geometry(int kind, int dense, uint64_t dim, int waves_per_chain, int jit_w, int jit_nv, int low_rank_metric, int no_register_kernel,
                                int no_stream_cache, int64_t* out, char* family_name);
+/* host-only: how the engine drives a job (csrc/drive_plan.h: choose_drive).  in[16] = kind, dense, n, dim, W, ld, manual, staging given, host_groups,
+ * host_persist, graph_steps, no_register_kernel, low_rank_metric, store_divergences, pause draws, CUs; out[17] = mode, zero_copy, n_groups, grp_lo[9],
+ * remote_nv, persist_evals, fall_back_after, graph_steps, first sequence number of a group */
+int nphip_test_choose_drive(const int64_t* in, int64_t* out);
 
 #ifdef __cplusplus
 }

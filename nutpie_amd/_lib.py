@@ -91,7 +91,7 @@ _lib_lock = threading.Lock()
 
 def build(force: bool = False) -> str:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("kernels.hip", "host.hip", "linalg.hip", "lowrank_est.hip", "engine_types.h", "kernel_families.h", "dense_tile.h", "Makefile")]
+    srcs = [os.path.join(_CSRC, f) for f in ("kernels.hip", "host.hip", "linalg.hip", "lowrank_est.hip", "engine_types.h", "kernel_families.h", "drive_plan.h", "dense_tile.h", "Makefile")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("nutpie_hip.h", "nphip_spec.h")]
     stale = not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -202,6 +202,7 @@ def lib():
             L.nphip_test_dot.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
             L.nphip_test_rowpool.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
             L.nphip_test_choose_geometry.argtypes = [C.c_int, C.c_int, C.c_uint64] + [C.c_int] * 6 + [C.POINTER(C.c_int64), C.c_char_p]
+            L.nphip_test_choose_drive.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             _lib = L
     return _lib
 
@@ -1051,6 +1052,25 @@ def test_choose_geometry(dim, *, kind=0, dense=False, waves_per_chain=0, jit_w=0
     g = {k: (int(v) if k in ("W", "family_id", "NV", "ld") else bool(v)) for k, v in zip(keys, out)}
     g["family"] = name.value.decode()
     return g
+
+
+DRIVE_MODES = ("in_kernel", "host_sync", "host_pipelined", "host_resident", "device", "device_groups")
+
+
+def test_choose_drive(n, dim, *, kind=1, dense=False, W=1, ld=None, manual=False, staging_given=False, host_groups=0, host_persist=0, graph_steps=0,
+                      no_register_kernel=False, low_rank_metric=False, store_divergences=False, n_pause=0, cus=256):
+    """Host-only: how the engine drives a job (csrc/drive_plan.h: choose_drive).  ``W`` and ``ld`` are the geometry's (``ld`` defaults to
+    the row length padded to whole chunks of 128); ``bounds`` are the groups' first chains and the chain count."""
+    if ld is None:
+        ld = (int(dim) + 127) // 128 * 128
+    vals = (kind, bool(dense), n, dim, W, ld, bool(manual), bool(staging_given), host_groups, host_persist, graph_steps, bool(no_register_kernel),
+            bool(low_rank_metric), bool(store_divergences), n_pause, cus)
+    out = (C.c_int64 * 17)()
+    if lib().nphip_test_choose_drive((C.c_int64 * 16)(*(int(v) for v in vals)), out) != NPHIP_OK:
+        raise RuntimeError(_err())
+    o = [int(v) for v in out]
+    return {"mode": DRIVE_MODES[o[0]], "zero_copy": bool(o[1]), "n_groups": o[2], "bounds": o[3:4 + o[2]] if o[2] else [], "grp_lo": o[3:12],
+            "remote_nv": o[12], "persist_evals": o[13], "fall_back_after": o[14], "graph_steps": o[15], "seq_first": o[16]}
 
 
 def test_detmath(fn: str, x, device=0):

@@ -27,6 +27,7 @@
 #include "../../include/nphip_spec.h"
 #include "engine_types.h"
 #include "kernel_families.h"
+#include "drive_plan.h"
 
 namespace nphip {
 hipError_t launch_advance(const Args& a, const Args* d_args, bool fused, int W, hipStream_t st, const LaunchSlice* slice = nullptr);
@@ -613,7 +614,12 @@ struct nphip_sampler {
     int W = 1;
     bool fused = true;
     bool dens = false;   // runtime-compiled device density: the resident kernel of the model's own library, driven like a fused model
-    bool zero_copy = false;  // host callbacks: staging buffers in pinned host memory, no copies
+    // how the job is driven (drive_plan.h: choose_drive): the plan as set-up made it, and the mode as it is now — the two fall-backs from a
+    // resident form assign it, nothing else does
+    DrivePlan plan;
+    Drive mode = Drive::in_kernel;
+    bool fell_back = false;
+    bool dense_resident() const { return mode == Drive::in_kernel && model.dense; }
     uint64_t n = 0, T = 0, dim = 0;
     std::vector<void*> allocs;
     std::vector<void*> pinned;
@@ -668,7 +674,6 @@ struct nphip_sampler {
     // evaluation in its middle — driven like a fused model (a launch runs `evals_per_launch` evaluations of every chain).  A launch whose
     // roll call fails (the device was busy: not every chain resident) has touched nothing and is simply repeated; after three in a row the
     // job goes on with a launch per evaluation.
-    bool dg = false, dg_fell_back = false;
     int dg_fail = 0;
     unsigned dg_launch_id = 0;
     unsigned long long dg_fail_seen = 0;
@@ -695,7 +700,7 @@ struct nphip_sampler {
     bool setup();
     void run();
     bool manual = false;
-    int manual_have = 0;
+    int manual_have = 0;   // callback models: the staging buffers hold the evaluation the next launch consumes
     // kernel timing (nphip_sampler_step with kernel_ms): one pair of HIP events around every launch, read after the last one
     std::vector<hipEvent_t> tev;
     size_t timed_launches = 0;
@@ -704,32 +709,44 @@ struct nphip_sampler {
     // two launches); the "all chains done" / error check therefore runs one launch behind
     hipEvent_t ev_f[2] = {nullptr, nullptr};
     uint64_t fused_k = 0;
-    bool check_counters(int slot, bool& all_done);
+    LaunchSlice slice_of(uint64_t lo, uint64_t cnt, int grp = -1) const {
+        LaunchSlice sl = LaunchSlice();   // (value-initialised: every byte of it goes to the kernel as a parameter)
+        sl.chain_lo = (int)lo; sl.chain_n = (int)cnt; sl.grp = grp;
+        return sl;
+    }
+    LaunchSlice slice_of_group(int g, int grp = -1) const { return slice_of(plan.grp_lo[g], plan.grp_lo[g + 1] - plan.grp_lo[g], grp); }
     bool launch_kernel(bool fused_, int have);
+    bool iterate(bool& all_done);
     bool iteration_fused(bool& all_done);
     bool iteration_graph(bool& all_done);
     hipGraphExec_t cb_graph = nullptr;
     hipEvent_t cb_ev[2] = {nullptr, nullptr};
-    int cb_graph_steps = 0;
     uint64_t cb_replays = 0;
     uint64_t cb_polls = 0;
-    bool iteration_callback(bool& all_done, int& have);
-    bool iteration_callback_groups(bool& all_done, int& have);
+    bool poll_counters(hipStream_t st);
+    bool counters_verdict(bool& all_done, int slot = 0);
+    // the model's device callback on the rows [lo, lo + cnt) of the staging buffers
+    int callback_rows(uint64_t lo, uint64_t cnt, hipStream_t st) {
+        return model.dev_fn(cnt, dim, args.qeval + lo * dim, args.geval + lo * dim, args.ueval + lo, (void*)st, model.user);
+    }
+    bool callback_failed(int rc) { (void)sync_all(); set_error("device logp callback failed (code " + std::to_string(rc) + ")"); return false; }
+    bool prime_groups() {   // everything enqueued on the main stream so far (set-up, the chains' start) precedes the groups' first launches
+        if (grp_primed) return true;
+        grp_primed = true;
+        return hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    }
+    bool iteration_host_sync(bool& all_done);
+    bool iteration_device(bool& all_done);
+    bool iteration_device_groups(bool& all_done);
     // host callbacks, zero-copy staging: chains in groups, each on its own stream, completion by a flag in pinned memory
     // (no stream synchronisation): the kernel of one group runs while the host evaluates the rows of the other
-    static constexpr int kMaxGroups = 8;
-    int n_groups = 0;
     hipStream_t grp_stream[kMaxGroups] = {};
-    uint64_t grp_lo[kMaxGroups + 1] = {};
     unsigned grp_seq[kMaxGroups] = {};
     bool grp_primed = false;
-    int cb_groups = 0;   // device callbacks in groups of chains (launch.host_groups >= 2): group g's (kernel, callback) on its own stream
     volatile unsigned long long* h_grp_flag = nullptr;  // pinned [groups][4]
     // Resident launches (kernels.hip: REMOTE): a group's kernel stays on the device for `persist_evals` evaluations; an evaluation
     // is a rendezvous — the kernel publishes its positions and the sequence number, the host evaluates the rows and answers
     // with one word in pinned memory.  grp_seq[g] is then the sequence number the host waits for next.
-    bool remote = false;
-    bool remote_fell_back = false;
     // resident launches on a large-BAR system: the results (gradient, logp, code) and the go words live in fine-grained DEVICE
     // memory that the host writes through the PCIe BAR (write-combining stores: 64 rows in ~0.25 us) — the kernel then polls
     // and reads local memory instead of host memory over PCIe (a read round trip each).  The callback itself still writes
@@ -739,13 +756,10 @@ struct nphip_sampler {
     int64_t* b_code = nullptr;
     volatile unsigned long long* b_go = nullptr;
     void publish_rows(uint64_t lo, uint64_t cnt);
-    int remote_nv = 0;
-    int persist_evals = 256;
     volatile unsigned long long* h_grp_go = nullptr;    // pinned [groups][8]
     bool grp_running[kMaxGroups] = {};
     int grp_evals[kMaxGroups] = {};
     bool materialise = false;   // the next callback launches follow resident ones (LaunchSlice::materialise)
-    int64_t fall_back_after = 0; // tests (launch.host_persist = -N): leave the resident mode after N evaluations, as a failed roll call would
     int64_t remote_evals = 0;
     bool bar_used = false;   // (diagnostics: the BAR copy was in use at some point of the job)
     double t_wait_ns = 0.0, t_eval_ns = 0.0;   // NPHIP_TIMING=1: where the driver thread's time goes (printed at the end of the job)
@@ -763,9 +777,9 @@ struct nphip_sampler {
     bool wait_group(int g);
     bool iteration_pipelined(bool& all_done);
     bool sync_all() {
-        if (remote && !drain_groups()) return false;
+        if (mode == Drive::host_resident && !drain_groups()) return false;
         bool ok = hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize");
-        for (int g = 0; g < n_groups; ++g) ok = hip_ok(hipStreamSynchronize(grp_stream[g]), "hipStreamSynchronize") && ok;
+        for (int g = 0; g < plan.n_groups; ++g) ok = hip_ok(hipStreamSynchronize(grp_stream[g]), "hipStreamSynchronize") && ok;
         return ok;
     }
     void fail(const std::string& msg) {
@@ -904,6 +918,16 @@ bool nphip_sampler::setup() {
                   " > " + std::to_string(set.num_chains) + ")");
         return false;
     }
+    // how the job is driven: the rules are choose_drive's (drive_plan.h); what follows acquires what its plan needs
+    DriveIn din;
+    din.kind = model.kind; din.dense = model.dense; din.n = n; din.dim = dim; din.W = W; din.ld = geo.ld; din.manual = launch.manual != 0;
+    din.staging_given = launch.staging_q && launch.staging_grad && launch.staging_logp;
+    din.host_groups = launch.host_groups; din.host_persist = launch.host_persist; din.graph_steps = launch.graph_steps;
+    din.no_register_kernel = launch.no_register_kernel != 0; din.low_rank_metric = lrm; din.store_divergences = set.store_divergences;
+    din.n_pause = (int)set.pause_draws.size();
+    if (model.dense && hipDeviceGetAttribute(&din.cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) din.cus = 0;
+    plan = choose_drive(din);
+    mode = plan.mode;
 
     memset(&args, 0, sizeof(args));
     DevSettings& s = args.s;
@@ -985,15 +1009,9 @@ bool nphip_sampler::setup() {
         HIP_TRY(hipMemcpyAsync(bsh, bshpad.data(), (ld + 8) * 8, hipMemcpyHostToDevice, stream));
         args.m_bsh = bsh;
     } else {
-        // Host callbacks with small batches are latency-bound (five copies + a synchronisation per leapfrog): there the
-        // staging buffers ARE the pinned host buffers (coherent, GPU-visible on ROCm) and the kernel reads / writes them
-        // over PCIe directly.  Larger batches keep device staging + bulk copies.
-        // (up to 4 MB of positions per step; 8 MB where resident launches apply — dim <= 1024, <= 1024 chains — which need them)
-        const uint64_t zc_limit = (n <= 1024 && dim <= 1024) ? (8u << 20) : (4u << 20);
-        zero_copy = (model.kind == 1) && !(launch.staging_q && launch.staging_grad && launch.staging_logp) && n * dim * 8 <= zc_limit;
-        if (launch.staging_q && launch.staging_grad && launch.staging_logp) {
+        if (din.staging_given) {
             args.qeval = (double*)launch.staging_q; args.geval = (double*)launch.staging_grad; args.ueval = (double*)launch.staging_logp;
-        } else if (!zero_copy && (!dalloc(&args.qeval, n * dim) || !dalloc(&args.geval, n * dim) || !dalloc(&args.ueval, n))) return false;
+        } else if (!plan.zero_copy && (!dalloc(&args.qeval, n * dim) || !dalloc(&args.geval, n * dim) || !dalloc(&args.ueval, n))) return false;
         if (dens) {
             args.dens_data = model.jit_data;
             args.dens_lds_doubles = (int32_t)(model.jit_lds_bytes / 8);
@@ -1001,44 +1019,22 @@ bool nphip_sampler::setup() {
             if ((int64_t)model.jit_nv * 128 * W != args.ld) { set_error("the density's library was compiled for another dimension (nv chunks)"); return false; }
         }
         if (model.kind == 1) {
-            if (!zero_copy && !dalloc(&args.ecode, n)) return false;
+            if (!plan.zero_copy && !dalloc(&args.ecode, n)) return false;
             if (!palloc(&h_q, n * dim) || !palloc(&h_g, n * dim) || !palloc(&h_u, n) || !palloc(&h_code, n)) return false;
-            if (zero_copy) { args.qeval = h_q; args.geval = h_g; args.ueval = h_u; args.ecode = h_code; }
+            if (plan.zero_copy) { args.qeval = h_q; args.geval = h_g; args.ueval = h_u; args.ecode = h_code; }
             // n_threads > 0: that many evaluation threads.  n_threads == 0: threads per batch from the measured cost of a row (eval_ranges)
             host_cores = usable_cores();
-            // pipelining: two groups of chains in flight — while the host evaluates the rows of one group the
-            // kernel of the other runs.  Zero-copy batches only (they are the latency-bound ones); launch.host_groups = 1 turns it off.
-            if (zero_copy && !launch.manual && launch.host_groups != 1 && n >= 2) {
-                // measured (profiles/r2_config4_host_callback_pipelining.txt): eight schools, 256 chains: 5.7 -> 6.5 (2 groups) -> 6.7 M
-                // leapfrogs/s (4 groups); 1024 chains: 12.3 -> 14.5 -> 16.2.  The rest of a step is fixed latency (launch, the
-                // memory-resident kernel's dependent passes, its PCIe reads of the gradients, the flag), which groups overlap with
-                // each other but cannot shorten — the resident launches below can (profiles/r2_config4_resident_launches.txt: 11.3
-                // and 20 M leapfrogs/s).
-                n_groups = (n >= 128) ? 4 : ((n >= 32) ? 2 : 1);
-                if (launch.host_groups >= 2 && launch.host_groups <= kMaxGroups) n_groups = (int)std::min<uint64_t>(launch.host_groups, n);
-                for (int g = 0; g <= n_groups; ++g) grp_lo[g] = n * (uint64_t)g / (uint64_t)n_groups;
-                if (!dalloc(&args.grp_arrive, kMaxGroups)) return false;
-                unsigned long long* f = nullptr;
-                if (!palloc(&f, 4 * kMaxGroups)) return false;
+            if (plan.n_groups > 0) {
+                // groups of chains (pipelined or resident): the completion flags and the go words in pinned memory
+                unsigned long long *f = nullptr, *go = nullptr;
+                if (!dalloc(&args.grp_arrive, kMaxGroups) || !palloc(&f, 4 * kMaxGroups)) return false;
                 h_grp_flag = f;
                 args.grp_flag = f;
-                // resident launches: one wave per chain with the state in registers (dim <= 1024); every chain of a group must be on
-                // the device at once (<= 1024 chains: a quarter of the wave slots); the adaptation hook edits control blocks
-                // between launches and the divergence record needs the pre-step state in memory — both keep a launch per evaluation
-                unsigned long long* go = nullptr;
                 if (!palloc(&go, 8 * kMaxGroups) || !dalloc(&args.grp_go_dev, 16 * kMaxGroups)) return false;
                 h_grp_go = go;
                 args.grp_go = go;
-                remote_nv = (int)(args.ld / 128 / W);
-                // (above 4 MB of positions per step the job is bound by PCIe traffic either way, and launches per evaluation were 15 %
-                //  faster at 1024 chains x 1000 dimensions: resident only when asked for)
-                remote = (has(kRemoteW1, W, remote_nv) || has(kRemoteWn, W, remote_nv)) && (int64_t)remote_nv * W * 128 == args.ld && n * (uint64_t)W <= 1024 &&
-                         launch.host_persist != 1 && !launch.no_register_kernel && !lrm &&
-                         !set.store_divergences && set.pause_draws.empty() && (n * dim * 8 <= (4u << 20) || launch.host_persist > 1);
-                persist_evals = launch.host_persist > 1 ? launch.host_persist : 256;
-                if (launch.host_persist < 0) { fall_back_after = -(int64_t)launch.host_persist; persist_evals = 7; }
-                for (int g = 0; g < kMaxGroups; ++g) grp_seq[g] = remote ? 1u : 0u;
-                if (remote && !getenv("NPHIP_NO_BAR")) {
+                for (int g = 0; g < kMaxGroups; ++g) grp_seq[g] = plan.seq_first;
+                if (mode == Drive::host_resident && !getenv("NPHIP_NO_BAR")) {
                     int large_bar = 0;
                     if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device) != hipSuccess) large_bar = 0;
                     void *pg = nullptr, *pu = nullptr, *pc = nullptr, *po = nullptr;
@@ -1058,21 +1054,10 @@ bool nphip_sampler::setup() {
                     }
                     for (void* q : {pg, pu, pc, po}) if (q) allocs.push_back(q);
                 }
-                if (remote) {
-                    // (a step of a resident group is ~20 us of device latency — PCIe round trips and one L2 write-back — and ~3 us of
-                    //  host work per 64 rows: eight groups keep the driver thread busy while seven of them are in flight)
-                    if (launch.host_groups == 0) n_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>(8, n / 8));
-                    // one wave per chain: a workgroup holds four chains, and they rendezvous as one (kernels.hip: remote_sync) — group
-                    // bounds on multiples of 4
-                    const uint64_t per_wg = (W == 1) ? 4 : 1, wgs = (n + per_wg - 1) / per_wg;
-                    n_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_groups, wgs));
-                    for (int g = 1; g < n_groups; ++g) grp_lo[g] = (wgs * (uint64_t)g / (uint64_t)n_groups) * per_wg;
-                    grp_lo[n_groups] = n;
-                }
-                for (int g = 0; g < n_groups; ++g) HIP_TRY(hipStreamCreateWithFlags(&grp_stream[g], hipStreamNonBlocking));
             }
         }
     }
+    for (int g = 0; g < plan.n_groups; ++g) HIP_TRY(hipStreamCreateWithFlags(&grp_stream[g], hipStreamNonBlocking));   // a stream per group of chains
     if (model.dense) {
         // Pp [DP][KP]: rows padded to a multiple of 16 elements and 64 rows with zeros (dense_tile.h reads whole fragments), mu [KP]
         const size_t KP = (dim + 15) / 16 * 16, DP = (dim + 63) / 64 * 64;
@@ -1083,20 +1068,8 @@ bool nphip_sampler::setup() {
         dense_dev.Pp = dP; dense_dev.mu = dmu; dense_dev.KP = (int64_t)KP; dense_dev.W = W;
         model.dev_fn = &nphip_sampler::dense_dev_fn;
         model.user = &dense_dev;
-        // the resident form: every chain on the device at once (one workgroup of four chains per CU), state in registers
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
-        // ... when the job is large enough for it: a cluster is formed from workgroups of ONE die (8 of them, workgroups dealt round-robin), and
-        // its members share the column tiles of the GEMM — with fewer than half as many workgroups per die as there are tiles (64 columns each)
-        // a member computes three or more tiles per round and a launch per evaluation is faster (measured, scratch/r6_dense_small.py:
-        // D = 1000: 128 chains 0.69 against 1.05 M leapfrogs/s, 256 chains 2.38 against 2.00; D = 256: 16 chains 0.28 against 0.52, 64 chains
-        // 1.59 against 1.39).  launch.host_persist > 1 forces the resident form.
-        const uint64_t wgs_per_die = std::max<uint64_t>(1, ((n + 3) / 4) / 8), n_tiles = (dim + 63) / 64;
-        const uint64_t tiles_per_member = (n_tiles + std::min<uint64_t>(16, wgs_per_die) - 1) / std::min<uint64_t>(16, wgs_per_die);
-        dg = has(kDenseResident, W, args.ld / 128) && (n + 3) / 4 <= (uint64_t)cus && !lrm && !set.store_divergences &&
-             set.pause_draws.empty() && !launch.no_register_kernel && launch.host_persist != 1 && launch.host_groups < 2 &&
-             (tiles_per_member <= 2 || launch.host_persist > 1);
-        if (dg) {
+        // the resident form (drive_plan.h): the register-resident leaf with the launch-wide GEMM as the evaluation in its middle
+        if (dense_resident()) {
             args.dg_P = dP; args.dg_mu = dmu; args.dg_KP = (int64_t)KP;
             { const char* e = getenv("NPHIP_DG_VARIANT"); args.dg_variant = e ? atoi(e) : 0; }
             args.reg_nv = (int32_t)(args.ld / 128);
@@ -1108,19 +1081,6 @@ bool nphip_sampler::setup() {
             if (!palloc(&ab, 2)) return false;
             h_dg_abort = ab;
         }
-    }
-    if (model.kind == 2 && launch.host_groups >= 2 && !launch.manual && n >= 8) {
-        // Device callbacks in groups (round 5): the chains in `host_groups` contiguous groups, each with a stream of its
-        // own on which its k_advance launch and its callback alternate — while one group's callback runs (a GEMM, a torch function) the
-        // other group's engine kernel does.  No flag and no host synchronisation: stream order is the only dependency, the callback
-        // gets the group's rows of the staging buffers (pointers offset, n_chains = the group's).  Bounds on whole workgroups.
-        const uint64_t per_wg = (W == 1) ? 4 : 1, wgs = (n + per_wg - 1) / per_wg;
-        n_groups = (int)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)launch.host_groups, (uint64_t)kMaxGroups, wgs}));
-        grp_lo[0] = 0;
-        for (int g = 1; g < n_groups; ++g) grp_lo[g] = (wgs * (uint64_t)g / (uint64_t)n_groups) * per_wg;
-        grp_lo[n_groups] = n;
-        for (int g = 0; g < n_groups; ++g) HIP_TRY(hipStreamCreateWithFlags(&grp_stream[g], hipStreamNonBlocking));
-        cb_groups = n_groups;
     }
     if (model.init_kind == 2) {
         if (model.n_init_points < launch.chain_offset + n) { set_error("explicit init points do not cover all chains"); return false; }
@@ -1167,7 +1127,8 @@ bool nphip_sampler::launch_kernel(bool fused_, int have) {
     // (a runtime-compiled density costs microseconds per evaluation: 512 per launch is milliseconds of kernel already, and the
     //  job's tail — chains that are done wait for the launch to end — shrinks with the launch)
     // (the dense Gaussian's resident form: an evaluation round of the whole launch is ~50 us at 1024 chains x 1000 dimensions)
-    args.max_evals = (fused_ || dens || dg) ? (launch.evals_per_launch > 0 ? launch.evals_per_launch : (dg ? 256 : (dens ? 512 : default_evals_per_launch(dim)))) : 0;
+    const bool dg = dense_resident();
+    args.max_evals = mode == Drive::in_kernel ? (launch.evals_per_launch > 0 ? launch.evals_per_launch : (dg ? 256 : (dens ? 512 : default_evals_per_launch(dim)))) : 0;
     args.have_result = have;
     if (kernel_ms_acc) {
         while (tev.size() < 2 * (timed_launches + 1)) {
@@ -1177,26 +1138,20 @@ bool nphip_sampler::launch_kernel(bool fused_, int have) {
         }
         if (!hip_ok(hipEventRecord(tev[2 * timed_launches], stream), "hipEventRecord")) return false;
     }
+    LaunchSlice sl = slice_of(0, n);
     if (dens) {
-        LaunchSlice sl;
-        memset(&sl, 0, sizeof(sl));
-        sl.chain_lo = 0; sl.chain_n = (int)n; sl.grp = -1;
         const uint64_t cpb = W == 1 ? 4 : 1;   // chains per workgroup
         const int rc = model.jit_launch(d_args, args.max_evals, (void*)stream, &sl,
                                         cpb * model.jit_lds_bytes + model.jit_shared_bytes + cpb * 2 * (uint64_t)args.ld * 8);
         if (rc != 0) { set_error(std::string("launch of the runtime-compiled density kernel: ") + hipGetErrorString((hipError_t)rc)); return false; }
     } else if (dg) {
-        LaunchSlice sl;
-        memset(&sl, 0, sizeof(sl));
-        sl.chain_lo = 0; sl.chain_n = (int)n; sl.grp = -1; sl.seq = ++dg_launch_id; sl.n_grp = 1;
+        sl.seq = ++dg_launch_id; sl.n_grp = 1;
         for (int g = 1; g <= kMaxGroups; ++g) sl.grp_lo[g] = (int)n;
         if (!hip_ok(hipMemsetAsync(args.dg_sync, 0, (size_t)kDgSyncWords * 8, stream), "hipMemsetAsync")) return false;
         if (!hip_ok(launch_dense_resident(d_args, args.reg_nv, args.max_evals, stream, sl), "launch k_advance (dense, resident)")) return false;
     } else if (materialise && model.dense) {
         // the launches before this one were resident ones (they defer the first half of a tree leapfrog into the leaf): this one performs it
-        LaunchSlice sl;
-        memset(&sl, 0, sizeof(sl));
-        sl.chain_lo = 0; sl.chain_n = (int)n; sl.grp = -1; sl.materialise = 1;
+        sl.materialise = 1;
         materialise = false;
         if (!hip_ok(launch_advance(args, d_args, fused_, W, stream, &sl), "launch k_advance")) return false;
     } else if (!hip_ok(launch_advance(args, d_args, fused_, W, stream), "launch k_advance")) return false;
@@ -1208,18 +1163,12 @@ bool nphip_sampler::launch_kernel(bool fused_, int have) {
     return true;
 }
 
-bool nphip_sampler::check_counters(int slot, bool& all_done) {
-    const unsigned long long* hc = h_counters + 2 * slot;
-    if (hc[1] > 0) { (void)hipStreamSynchronize(stream); set_error(chain_error_message()); return false; }
-    all_done = hc[0] >= n;
-    return true;
-}
-
 bool nphip_sampler::iteration_fused(bool& all_done) {
     const int slot = (int)(fused_k & 1);
     if (!ev_f[0] && (!hip_ok(hipEventCreateWithFlags(&ev_f[0], hipEventDisableTiming), "hipEventCreate") ||
                      !hip_ok(hipEventCreateWithFlags(&ev_f[1], hipEventDisableTiming), "hipEventCreate"))) return false;
-    if (!launch_kernel(!dens && !dg, 0)) return false;
+    const bool dg = dense_resident();   // (before the launch is looked at: dg_check may leave the resident form)
+    if (!launch_kernel(fused, 0)) return false;
     if (!hip_ok(hipMemcpyAsync(h_counters + 2 * slot, args.counters, 16, hipMemcpyDeviceToHost, stream), "copy counters")) return false;
     if (dg && !hip_ok(hipMemcpyAsync((void*)(h_dg_abort + slot), args.dg_sync + (size_t)128 * 32, 8, hipMemcpyDeviceToHost, stream), "copy abort word")) return false;
     if (!hip_ok(hipEventRecord(ev_f[slot], stream), "hipEventRecord")) return false;
@@ -1228,7 +1177,7 @@ bool nphip_sampler::iteration_fused(bool& all_done) {
     // the launch before this one: by now it has the device to itself no longer — its successor is queued behind it
     if (!hip_ok(hipEventSynchronize(ev_f[slot ^ 1]), "hipEventSynchronize")) return false;
     if (dg && !dg_check(slot ^ 1)) return false;
-    return check_counters(slot ^ 1, all_done);
+    return counters_verdict(all_done, slot ^ 1);
 }
 
 // The dense Gaussian's resident launches, looked at one launch late (as the counters are): a rendezvous that timed out is an error (it
@@ -1250,8 +1199,8 @@ bool nphip_sampler::dg_check(int slot) {
         if (++dg_fail >= 3) {
             // the device does not hold all chains at once (something else is running on it): a launch per evaluation from here on
             if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize")) return false;
-            dg = false;
-            dg_fell_back = true;
+            mode = Drive::device;
+            fell_back = true;
             materialise = true;
             manual_have = 0;
             fused_k = 0;
@@ -1305,144 +1254,122 @@ void nphip_sampler::eval_ranges(const RowRange* rg, int nr) {
     timed_batches += 1;
 }
 
-// Device callbacks in groups: one step of every group.  The first step runs on the main stream (it follows the set-up work there).
-bool nphip_sampler::iteration_callback_groups(bool& all_done, int& have) {
+// Device callbacks: the done / error counters are polled without synchronising (stale values only delay the exit), and only every
+// eighth step: the 16-byte copy is a 5 us kernel in the same stream (13 % of a step with a one-kernel model).  The copies sit behind a
+// two-slot event, so the host stays at most sixteen steps ahead of the device: without a bound it enqueues thousands of launches while
+// the device works through the first ones, and when the last chain finishes the device still has all of them to run (measured: 11 089
+// launches for a job of 3 425 evaluation steps).
+bool nphip_sampler::poll_counters(hipStream_t st) {
     if ((cb_polls & 7) == 0) {
         const int slot = (int)((cb_polls >> 3) & 1);
         if (!cb_ev[slot] && !hip_ok(hipEventCreate(&cb_ev[slot]), "hipEventCreate")) return false;
         if (cb_polls >= 16 && !hip_ok(hipEventSynchronize(cb_ev[slot]), "hipEventSynchronize")) return false;
-        if (!hip_ok(hipMemcpyAsync(h_counters, args.counters, 16, hipMemcpyDeviceToHost, grp_stream[n_groups - 1]), "copy counters")) return false;
-        if (!hip_ok(hipEventRecord(cb_ev[slot], grp_stream[n_groups - 1]), "hipEventRecord")) return false;
+        if (!hip_ok(hipMemcpyAsync(h_counters, args.counters, 16, hipMemcpyDeviceToHost, st), "copy counters")) return false;
+        if (!hip_ok(hipEventRecord(cb_ev[slot], st), "hipEventRecord")) return false;
     }
     ++cb_polls;
-    volatile unsigned long long* hc = h_counters;
-    if (hc[1] > 0) {
-        for (int g = 0; g < n_groups; ++g) (void)hipStreamSynchronize(grp_stream[g]);
-        set_error(chain_error_message());
-        return false;
-    }
-    if (hc[0] >= n) {
-        all_done = true;
-        for (int g = 0; g < n_groups; ++g)
-            if (!hip_ok(hipStreamSynchronize(grp_stream[g]), "hipStreamSynchronize")) return false;
-        return true;
-    }
-    for (int g = 0; g < n_groups; ++g) {
-        LaunchSlice sl;
-        memset(&sl, 0, sizeof(sl));
-        sl.chain_lo = (int)grp_lo[g];
-        sl.chain_n = (int)(grp_lo[g + 1] - grp_lo[g]);
-        sl.grp = -1;
-        sl.materialise = materialise ? 1 : 0;
-        args.max_evals = 0;
-        args.have_result = have;
-        if (!hip_ok(launch_advance(args, d_args, false, W, grp_stream[g], &sl), "launch k_advance")) return false;
-        launches.fetch_add(g == 0 ? 1 : 0);    // (a step of all groups counts once)
-        const uint64_t lo = grp_lo[g];
-        const int rc = model.dev_fn((uint64_t)sl.chain_n, dim, args.qeval + lo * dim, args.geval + lo * dim, args.ueval + lo, (void*)grp_stream[g], model.user);
-        if (rc < 0) {
-            for (int o = 0; o < n_groups; ++o) (void)hipStreamSynchronize(grp_stream[o]);
-            set_error("device logp callback failed (code " + std::to_string(rc) + ")");
-            return false;
-        }
-    }
-    materialise = false;
-    have = 1;
     return true;
 }
 
-bool nphip_sampler::iteration_callback(bool& all_done, int& have) {
-    if (model.kind == 2 && cb_graph_steps > 0 && have == 1 && !kernel_ms_acc) {
-        if (cb_groups > 1 && !cb_graph) {   // the steps before the capture ran on the groups' streams: the graph (launched on the main one) follows them
-            for (int g = 0; g < n_groups; ++g)
-                if (!hip_ok(hipStreamSynchronize(grp_stream[g]), "hipStreamSynchronize")) return false;
-        }
+// What the counters last copied (into `slot`) say: a chain in error ends the job (false); all chains done sets all_done.  Either way
+// nothing is left in flight on any stream: every loop's exit synchronises all of them (sync_all), once per job.
+bool nphip_sampler::counters_verdict(bool& all_done, int slot) {
+    volatile unsigned long long* hc = h_counters + 2 * slot;
+    if (hc[1] > 0) { (void)sync_all(); set_error(chain_error_message()); return false; }
+    all_done = hc[0] >= n;
+    return !all_done || sync_all();
+}
+
+// Device callbacks in groups: one step of every group, each on its own stream; the counters travel on the last group's.
+bool nphip_sampler::iteration_device_groups(bool& all_done) {
+    // (kernel timing, nphip_sampler_step's kernel_ms, needs manual mode, and the plan forms no groups there: no timed launch passes here)
+    if (plan.graph_steps > 0 && manual_have == 1) {
+        // the steps before the capture ran on the groups' streams: the graph (launched on the main one) follows them
+        if (!cb_graph && !sync_all()) return false;
         return iteration_graph(all_done);
     }
-    if (model.kind == 2 && cb_groups > 1 && !kernel_ms_acc) {
-        if (!grp_primed) {   // everything enqueued on the main stream so far (set-up, the chains' start) precedes the groups' first launches
-            if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize")) return false;
-            grp_primed = true;
-        }
-        return iteration_callback_groups(all_done, have);
+    if (!prime_groups() || !poll_counters(grp_stream[plan.n_groups - 1]) || !counters_verdict(all_done)) return false;
+    if (all_done) return true;
+    args.max_evals = 0;
+    args.have_result = manual_have;
+    for (int g = 0; g < plan.n_groups; ++g) {
+        LaunchSlice sl = slice_of_group(g);
+        sl.materialise = materialise ? 1 : 0;
+        if (!hip_ok(launch_advance(args, d_args, false, W, grp_stream[g], &sl), "launch k_advance")) return false;
+        launches.fetch_add(g == 0 ? 1 : 0);    // (a step of all groups counts once)
+        const int rc = callback_rows(plan.grp_lo[g], (uint64_t)sl.chain_n, grp_stream[g]);
+        if (rc < 0) return callback_failed(rc);
     }
-    if (!launch_kernel(false, have)) return false;
-    if (model.kind == 1) {
-        // host callback: D2H positions, evaluate rows on the host pool, H2D gradients
-        // (pinned hipMemcpyAsync; the reference calls the same function pointer once per
-        // chain-step from its worker threads: src/pymc.rs:197-215)
-        if (!zero_copy && !hip_ok(hipMemcpyAsync(h_q, args.qeval, n * dim * 8, hipMemcpyDeviceToHost, stream), "D2H q")) return false;
-        if (!hip_ok(hipMemcpyAsync(h_counters, args.counters, 16, hipMemcpyDeviceToHost, stream), "copy counters")) return false;
-        if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize")) return false;
-        if (h_counters[1] > 0) { set_error(chain_error_message()); return false; }
-        if (h_counters[0] >= n) { all_done = true; return true; }
-        const uint64_t d = dim;
-        (void)d;
-        eval_rows(0, n);
-        if (!zero_copy) {
-            if (!hip_ok(hipMemcpyAsync(args.geval, h_g, n * dim * 8, hipMemcpyHostToDevice, stream), "H2D grad")) return false;
-            if (!hip_ok(hipMemcpyAsync(args.ueval, h_u, n * 8, hipMemcpyHostToDevice, stream), "H2D logp")) return false;
-            if (!hip_ok(hipMemcpyAsync(args.ecode, h_code, n * 8, hipMemcpyHostToDevice, stream), "H2D code")) return false;
-        }
-    } else {
-        // device callback: counters are polled without synchronising (stale values only delay exit), and only every
-        // eighth step: the 16-byte copy is a 5 us kernel in the same stream (13 % of a step with a one-kernel model)
-        // ... and the host stays at most sixteen steps ahead of the device: without a bound it enqueues thousands of launches while
-        // the device works through the first ones, and when the last chain finishes the device still has all of them to run
-        // (measured: 11 089 launches for a job of 3 425 evaluation steps)
-        if ((cb_polls & 7) == 0) {
-            const int slot = (int)((cb_polls >> 3) & 1);
-            if (!cb_ev[slot] && !hip_ok(hipEventCreate(&cb_ev[slot]), "hipEventCreate")) return false;
-            if (cb_polls >= 16 && !hip_ok(hipEventSynchronize(cb_ev[slot]), "hipEventSynchronize")) return false;
-            if (!hip_ok(hipMemcpyAsync(h_counters, args.counters, 16, hipMemcpyDeviceToHost, stream), "copy counters")) return false;
-            if (!hip_ok(hipEventRecord(cb_ev[slot], stream), "hipEventRecord")) return false;
-        }
-        ++cb_polls;
-        volatile unsigned long long* hc = h_counters;
-        if (hc[1] > 0) {
-            (void)hipStreamSynchronize(stream);
-            set_error(chain_error_message());
-            return false;
-        }
-        if (hc[0] >= n) { all_done = true; return hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
-        int rc = model.dev_fn(n, dim, args.qeval, args.geval, args.ueval, (void*)stream, model.user);
-        if (rc < 0) {
-            (void)hipStreamSynchronize(stream);
-            set_error("device logp callback failed (code " + std::to_string(rc) + ")");
-            return false;
-        }
-    }
-    have = 1;
+    materialise = false;
+    manual_have = 1;
     return true;
 }
 
-// Device-callback models, steady state: `cb_graph_steps` x (engine kernel, model callback) captured once in a HIP graph
+// Host callback, one launch per evaluation: D2H positions, evaluate the rows on the host pool, H2D gradients (pinned hipMemcpyAsync; the
+// reference calls the same function pointer once per chain-step from its worker threads: src/pymc.rs:197-215).  Zero-copy staging
+// needs none of the copies.
+bool nphip_sampler::iteration_host_sync(bool& all_done) {
+    if (!launch_kernel(false, manual_have)) return false;
+    if (!plan.zero_copy && !hip_ok(hipMemcpyAsync(h_q, args.qeval, n * dim * 8, hipMemcpyDeviceToHost, stream), "D2H q")) return false;
+    if (!hip_ok(hipMemcpyAsync(h_counters, args.counters, 16, hipMemcpyDeviceToHost, stream), "copy counters")) return false;
+    if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize")) return false;
+    if (h_counters[1] > 0) { set_error(chain_error_message()); return false; }
+    if (h_counters[0] >= n) { all_done = true; return true; }
+    eval_rows(0, n);
+    if (!plan.zero_copy) {
+        if (!hip_ok(hipMemcpyAsync(args.geval, h_g, n * dim * 8, hipMemcpyHostToDevice, stream), "H2D grad")) return false;
+        if (!hip_ok(hipMemcpyAsync(args.ueval, h_u, n * 8, hipMemcpyHostToDevice, stream), "H2D logp")) return false;
+        if (!hip_ok(hipMemcpyAsync(args.ecode, h_code, n * 8, hipMemcpyHostToDevice, stream), "H2D code")) return false;
+    }
+    manual_have = 1;
+    return true;
+}
+
+// Device callback on the main stream: the engine kernel, then the model's callback behind it; the steady state from a captured graph.
+bool nphip_sampler::iteration_device(bool& all_done) {
+    if (plan.graph_steps > 0 && manual_have == 1 && !kernel_ms_acc) return iteration_graph(all_done);
+    if (!launch_kernel(false, manual_have)) return false;
+    if (!poll_counters(stream) || !counters_verdict(all_done)) return false;
+    if (all_done) return true;
+    const int rc = callback_rows(0, n, stream);
+    if (rc < 0) return callback_failed(rc);
+    manual_have = 1;
+    return true;
+}
+
+bool nphip_sampler::iterate(bool& all_done) {
+    switch (mode) {
+    case Drive::in_kernel: return iteration_fused(all_done);
+    case Drive::host_sync: return iteration_host_sync(all_done);
+    case Drive::host_pipelined: return iteration_pipelined(all_done);
+    case Drive::host_resident: return iteration_remote(all_done);
+    case Drive::device: return iteration_device(all_done);
+    case Drive::device_groups: return iteration_device_groups(all_done);
+    }
+    return false;
+}
+
+// Device-callback models, steady state: `plan.graph_steps` x (engine kernel, model callback) captured once in a HIP graph
 // and replayed — one host call per run of leapfrogs instead of two launches per leapfrog.  At most two replays are in
 // flight (the host must not run ahead of the done / error counters by more than that).
 bool nphip_sampler::iteration_graph(bool& all_done) {
     if (!cb_graph) {
         hipGraph_t g = nullptr;
         bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) == hipSuccess;
-        if (ok && cb_groups > 1) {
+        args.max_evals = 0;
+        args.have_result = 1;
+        if (ok && mode == Drive::device_groups) {
             // groups of chains as parallel branches of ONE graph (round 5): the capture forks from the main stream into every group's stream,
-            // each branch is that group's `cb_graph_steps` x (k_advance slice, callback on the group's rows), and joins again — the device
-            // overlaps one group's callback with another's kernel, and the host launches one graph per `cb_graph_steps` steps
-            args.max_evals = 0;
-            args.have_result = 1;
+            // each branch is that group's `plan.graph_steps` x (k_advance slice, callback on the group's rows), and joins again — the device
+            // overlaps one group's callback with another's kernel, and the host launches one graph per `plan.graph_steps` steps
             hipEvent_t fork = nullptr;
             ok = hipEventCreateWithFlags(&fork, hipEventDisableTiming) == hipSuccess && hipEventRecord(fork, stream) == hipSuccess;
-            std::vector<hipEvent_t> joins((size_t)n_groups, nullptr);
-            for (int gi = 0; ok && gi < n_groups; ++gi) {
+            std::vector<hipEvent_t> joins((size_t)plan.n_groups, nullptr);
+            for (int gi = 0; ok && gi < plan.n_groups; ++gi) {
                 ok = hipStreamWaitEvent(grp_stream[gi], fork, 0) == hipSuccess;
-                LaunchSlice sl;
-                memset(&sl, 0, sizeof(sl));
-                sl.chain_lo = (int)grp_lo[gi];
-                sl.chain_n = (int)(grp_lo[gi + 1] - grp_lo[gi]);
-                sl.grp = -1;
-                const uint64_t lo = grp_lo[gi];
-                for (int i = 0; ok && i < cb_graph_steps; ++i)
-                    ok = launch_advance(args, d_args, false, W, grp_stream[gi], &sl) == hipSuccess &&
-                         model.dev_fn((uint64_t)sl.chain_n, dim, args.qeval + lo * dim, args.geval + lo * dim, args.ueval + lo, (void*)grp_stream[gi], model.user) >= 0;
+                const LaunchSlice sl = slice_of_group(gi);
+                for (int i = 0; ok && i < plan.graph_steps; ++i)
+                    ok = launch_advance(args, d_args, false, W, grp_stream[gi], &sl) == hipSuccess && callback_rows(plan.grp_lo[gi], (uint64_t)sl.chain_n, grp_stream[gi]) >= 0;
                 ok = ok && hipEventCreateWithFlags(&joins[(size_t)gi], hipEventDisableTiming) == hipSuccess &&
                      hipEventRecord(joins[(size_t)gi], grp_stream[gi]) == hipSuccess && hipStreamWaitEvent(stream, joins[(size_t)gi], 0) == hipSuccess;
             }
@@ -1450,12 +1377,7 @@ bool nphip_sampler::iteration_graph(bool& all_done) {
             if (fork) (void)hipEventDestroy(fork);
             for (hipEvent_t e : joins) if (e) (void)hipEventDestroy(e);
         } else if (ok) {
-            args.max_evals = 0;
-            args.have_result = 1;
-            for (int i = 0; ok && i < cb_graph_steps; ++i) {
-                ok = launch_advance(args, d_args, false, W, stream) == hipSuccess &&
-                     model.dev_fn(n, dim, args.qeval, args.geval, args.ueval, (void*)stream, model.user) >= 0;
-            }
+            for (int i = 0; ok && i < plan.graph_steps; ++i) ok = launch_advance(args, d_args, false, W, stream) == hipSuccess && callback_rows(0, n, stream) >= 0;
             ok = (hipStreamEndCapture(stream, &g) == hipSuccess) && ok && g != nullptr;
         }
         if (ok) ok = hipGraphInstantiate(&cb_graph, g, nullptr, nullptr, 0) == hipSuccess;
@@ -1464,9 +1386,8 @@ bool nphip_sampler::iteration_graph(bool& all_done) {
             if (getenv("NPHIP_DEBUG")) fprintf(stderr, "nphip: graph_steps: the (kernel, callback) sequence could not be captured (%s): stepping without a graph\n", hipGetErrorString(hipGetLastError()));
             (void)hipGetLastError();
             cb_graph = nullptr;
-            cb_graph_steps = 0;
-            int have = 1;
-            return iteration_callback(all_done, have);
+            plan.graph_steps = 0;
+            return iterate(all_done);
         }
         for (auto& e : cb_ev)
             if (!e && !hip_ok(hipEventCreate(&e), "hipEventCreate")) return false;
@@ -1477,22 +1398,12 @@ bool nphip_sampler::iteration_graph(bool& all_done) {
     if (!hip_ok(hipMemcpyAsync(h_counters, args.counters, 16, hipMemcpyDeviceToHost, stream), "copy counters")) return false;
     if (!hip_ok(hipEventRecord(cb_ev[slot], stream), "hipEventRecord")) return false;
     cb_replays += 1;
-    launches.fetch_add((uint64_t)cb_graph_steps);
-    volatile unsigned long long* hc = h_counters;
-    if (hc[1] > 0) {
-        (void)hipStreamSynchronize(stream);
-        set_error(chain_error_message());
-        return false;
-    }
-    if (hc[0] >= n) { all_done = true; return hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
-    return true;
+    launches.fetch_add((uint64_t)plan.graph_steps);
+    return counters_verdict(all_done);
 }
 
 bool nphip_sampler::launch_group(int g, int have) {
-    LaunchSlice sl;
-    sl.chain_lo = (int)grp_lo[g];
-    sl.chain_n = (int)(grp_lo[g + 1] - grp_lo[g]);
-    sl.grp = g;
+    LaunchSlice sl = slice_of_group(g, g);
     sl.seq = ++grp_seq[g];
     sl.materialise = materialise ? 1 : 0;
     args.max_evals = 0;
@@ -1527,30 +1438,26 @@ bool nphip_sampler::wait_group(int g) {
 // ONE launch covers all groups: HIP multiplexes streams onto a few hardware queues, and a group's kernel queued behind another
 // group's resident kernel would never start while the host waits for it.
 bool nphip_sampler::launch_remote_all() {
-    LaunchSlice sl;
-    sl.chain_lo = 0;
-    sl.chain_n = (int)n;
-    sl.grp = 0;
+    LaunchSlice sl = slice_of(0, n, 0);
     sl.seq = ++remote_launch_id;
-    sl.materialise = 0;
-    sl.n_grp = n_groups;
+    sl.n_grp = plan.n_groups;
     if (bar && remote_evals >= 64) {
         // The BAR copy of the results takes PCIe reads off the device's critical path and costs the driver thread the copy.  It
         // pays while the device is what the job waits for; once a round of host work (every group's rows) is longer than a
         // device step (~20 us) the host is the bound and the copy only adds to it: back to results in host memory (launch boundary:
         // nothing is in flight).  Measured: eight schools, 256 chains 10.5 -> 12.2 M leapfrogs/s with the copy, 1024 chains 19.5 -> 16.3.
-        const double host_round_us = (double)n_groups * (t_eval_ns / (double)remote_evals + 800.0) * 1e-3;
+        const double host_round_us = (double)plan.n_groups * (t_eval_ns / (double)remote_evals + 800.0) * 1e-3;
         if (host_round_us > 25.0) {
             bar = false;
             args.geval = h_g; args.ueval = h_u; args.ecode = h_code; args.grp_go = h_grp_go;
-            for (int g = 0; g < n_groups; ++g) h_grp_go[8 * g] = 0ull;
+            for (int g = 0; g < plan.n_groups; ++g) h_grp_go[8 * g] = 0ull;
             if (!hip_ok(hipMemcpyAsync(d_args, &args, sizeof(Args), hipMemcpyHostToDevice, grp_stream[0]), "update args")) return false;
         }
     }
-    for (int g = 0; g <= kMaxGroups; ++g) sl.grp_lo[g] = (int)grp_lo[std::min(g, n_groups)];
+    for (int g = 0; g <= kMaxGroups; ++g) sl.grp_lo[g] = (int)plan.grp_lo[std::min(g, plan.n_groups)];
     for (int g = 0; g < kMaxGroups; ++g) sl.grp_seq[g] = grp_seq[g];   // a group's first evaluation carries the number the host waits for
-    if (!hip_ok(launch_remote(d_args, W, remote_nv, grp_stream[0], sl), "launch k_advance (resident)")) return false;
-    for (int g = 0; g < n_groups; ++g) { grp_running[g] = true; grp_evals[g] = 0; }
+    if (!hip_ok(launch_remote(d_args, W, plan.remote_nv, grp_stream[0], sl), "launch k_advance (resident)")) return false;
+    for (int g = 0; g < plan.n_groups; ++g) { grp_running[g] = true; grp_evals[g] = 0; }
     remote_fresh = true;
     return true;
 }
@@ -1567,9 +1474,9 @@ inline int nphip_sampler::poll_remote(int g) {
 int nphip_sampler::wait_remote(int only) {
     const auto t0 = std::chrono::steady_clock::now();
     for (uint64_t spin = 1;; ++spin) {
-        for (int g = 0; g < n_groups; ++g) {
-            const int o = (remote_next + g) % n_groups;
-            if ((only < 0 || o == only) && grp_running[o] && poll_remote(o)) { remote_next = (o + 1) % n_groups; remote_fresh = false; return o; }
+        for (int g = 0; g < plan.n_groups; ++g) {
+            const int o = (remote_next + g) % plan.n_groups;
+            if ((only < 0 || o == only) && grp_running[o] && poll_remote(o)) { remote_next = (o + 1) % plan.n_groups; remote_fresh = false; return o; }
         }
         if ((spin & 0xff) == 0) {
             if (remote_fresh && h_grp_flag[3] == (unsigned long long)remote_launch_id) return -2;
@@ -1578,7 +1485,7 @@ int nphip_sampler::wait_remote(int only) {
                 if (q != hipSuccess && q != hipErrorNotReady) { (void)hip_ok(q, "resident launch"); return -1; }
                 if (q == hipSuccess) {
                     bool any = false;
-                    for (int g = 0; g < n_groups; ++g) any = any || (grp_running[g] && poll_remote(g));
+                    for (int g = 0; g < plan.n_groups; ++g) any = any || (grp_running[g] && poll_remote(g));
                     if (!any && !(remote_fresh && h_grp_flag[3] == (unsigned long long)remote_launch_id)) {
                         set_error("resident host-callback launch ended without publishing its evaluation");
                         return -1;
@@ -1625,13 +1532,13 @@ void nphip_sampler::answer_group(int g, bool last) {
 // Bring the resident launch to its next boundary: one more evaluation of every group still in it, answered with kGoLast.  (A
 // chain's state only exists in memory at a boundary — whoever wants to read it, pause, abort or finish goes through here.)
 bool nphip_sampler::drain_groups() {
-    for (int g = 0; g < n_groups; ++g) {
+    for (int g = 0; g < plan.n_groups; ++g) {
         if (!grp_running[g]) continue;
         const int w = wait_remote(g);
         if (w == -1) return false;
-        if (w == -2) { for (int o = 0; o < n_groups; ++o) grp_running[o] = false; break; }   // nothing ran
-        eval_rows(grp_lo[g], grp_lo[g + 1] - grp_lo[g]);
-        publish_rows(grp_lo[g], grp_lo[g + 1] - grp_lo[g]);
+        if (w == -2) { for (int o = 0; o < plan.n_groups; ++o) grp_running[o] = false; break; }   // nothing ran
+        eval_rows(plan.grp_lo[g], plan.grp_lo[g + 1] - plan.grp_lo[g]);
+        publish_rows(plan.grp_lo[g], plan.grp_lo[g + 1] - plan.grp_lo[g]);
         answer_group(g, true);
     }
     return true;
@@ -1640,9 +1547,9 @@ bool nphip_sampler::drain_groups() {
 // The device could not hold all chains at once (roll call, kernels.hip): back to one launch per evaluation, for good.
 bool nphip_sampler::remote_fall_back() {
     if (!drain_groups()) return false;
-    remote = false;
-    remote_fell_back = true;
-    for (int g = 0; g < n_groups; ++g)
+    mode = Drive::host_pipelined;
+    fell_back = true;
+    for (int g = 0; g < plan.n_groups; ++g)
         if (!hip_ok(hipStreamSynchronize(grp_stream[g]), "hipStreamSynchronize")) return false;
     if (bar) {
         // launches per evaluation read the host's rows directly
@@ -1659,34 +1566,31 @@ bool nphip_sampler::remote_fall_back() {
 // cheap callback the groups come one at a time and the device is what the job waits for; with an expensive one all the other
 // groups publish while a batch is being evaluated, and the batches grow until the evaluation pool is busy.)
 bool nphip_sampler::iteration_remote(bool& all_done) {
-    if (!grp_primed) {
-        if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize")) return false;   // set-up copies ran on the main stream
-        grp_primed = true;
-    }
-    for (int served = 0; served < n_groups;) {
-        if (fall_back_after > 0 && remote_evals >= fall_back_after) return remote_fall_back();
+    if (!prime_groups()) return false;
+    for (int served = 0; served < plan.n_groups;) {
+        if (plan.fall_back_after > 0 && remote_evals >= plan.fall_back_after) return remote_fall_back();
         bool any = false;
-        for (int g = 0; g < n_groups; ++g) any = any || grp_running[g];
+        for (int g = 0; g < plan.n_groups; ++g) any = any || grp_running[g];
         if (!any && !launch_remote_all()) return false;
         const auto tw0 = std::chrono::steady_clock::now();
         const int first = wait_remote(-1);
         const auto tw1 = std::chrono::steady_clock::now();
         t_wait_ns += std::chrono::duration<double, std::nano>(tw1 - tw0).count();
         if (first == -1) return false;
-        if (first == -2) { for (int o = 0; o < n_groups; ++o) grp_running[o] = false; return remote_fall_back(); }
+        if (first == -2) { for (int o = 0; o < plan.n_groups; ++o) grp_running[o] = false; return remote_fall_back(); }
         int ready[kMaxGroups];
         RowRange rg[kMaxGroups];
         int nr = 0;
         // (looking at the other groups' flags costs a cache miss each: only when a batch is long enough for them to have published)
-        const bool gather = model.n_threads > 1 || (timed_batches >= 4 && row_ns * (double)(grp_lo[first + 1] - grp_lo[first]) > 8000.0);
-        for (int k = 0; k < (gather ? n_groups : 1); ++k) {
-            const int g = (first + k) % n_groups;
+        const bool gather = model.n_threads > 1 || (timed_batches >= 4 && row_ns * (double)(plan.grp_lo[first + 1] - plan.grp_lo[first]) > 8000.0);
+        for (int k = 0; k < (gather ? plan.n_groups : 1); ++k) {
+            const int g = (first + k) % plan.n_groups;
             if (!grp_running[g] || (g != first && !poll_remote(g))) continue;
             const unsigned long long pub = h_grp_flag[4 * g];
             if (pub & kPubError) { (void)sync_all(); set_error(chain_error_message()); return false; }
             if (pub & kPubAllDone) { all_done = true; return sync_all(); }
             ready[nr] = g;
-            rg[nr] = RowRange{grp_lo[g], grp_lo[g + 1] - grp_lo[g]};
+            rg[nr] = RowRange{plan.grp_lo[g], plan.grp_lo[g + 1] - plan.grp_lo[g]};
             nr += 1;
         }
         eval_ranges(rg, nr);
@@ -1696,7 +1600,7 @@ bool nphip_sampler::iteration_remote(bool& all_done) {
             const int g = ready[k];
             grp_evals[g] += 1;
             remote_evals += 1;
-            answer_group(g, grp_evals[g] >= persist_evals);
+            answer_group(g, grp_evals[g] >= plan.persist_evals);
         }
         served += nr;
     }
@@ -1707,25 +1611,23 @@ bool nphip_sampler::iteration_remote(bool& all_done) {
 bool nphip_sampler::iteration_pipelined(bool& all_done) {
     if (!grp_primed) {
         if (!hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize")) return false;   // set-up copies ran on the main stream
-        for (int g = 0; g < n_groups; ++g)
+        for (int g = 0; g < plan.n_groups; ++g)
             if (!launch_group(g, 0)) return false;
         grp_primed = true;
         materialise = false;
     }
-    const uint64_t d = dim;
-    for (int g = 0; g < n_groups; ++g) {
+    for (int g = 0; g < plan.n_groups; ++g) {
         if (!wait_group(g)) return false;
         volatile unsigned long long* f = h_grp_flag + 4 * g;
         if (f[2] > 0) { (void)sync_all(); set_error(chain_error_message()); return false; }
         if (f[1] >= n) {
             // every chain of the job is done; drain the launches still in flight for the other groups
-            for (int o = 0; o < n_groups; ++o)
+            for (int o = 0; o < plan.n_groups; ++o)
                 if (o != g && !wait_group(o)) return false;
             all_done = true;
             return sync_all();
         }
-        const uint64_t lo = grp_lo[g], cnt = grp_lo[g + 1] - lo;
-        (void)d;
+        const uint64_t lo = plan.grp_lo[g], cnt = plan.grp_lo[g + 1] - lo;
         eval_rows(lo, cnt);
         std::atomic_thread_fence(std::memory_order_release);
         if (!launch_group(g, 1)) return false;
@@ -1736,12 +1638,11 @@ bool nphip_sampler::iteration_pipelined(bool& all_done) {
 void nphip_sampler::run() {
     (void)hipSetDevice(device);
     t_start = std::chrono::steady_clock::now();
-    int have = 0;
     bool all_done = false;
     for (;;) {
         {
             std::unique_lock<std::mutex> lk(mu);
-            if (want_pause && !want_abort && remote) {
+            if (want_pause && !want_abort && mode == Drive::host_resident) {
                 // a resident launch would sit on the device for the whole pause (and hold up whatever shares its hardware queue):
                 // bring it to its boundary first
                 lk.unlock();
@@ -1754,7 +1655,7 @@ void nphip_sampler::run() {
         bool ok;
         {
             std::lock_guard<std::mutex> run_lk(mu_run);
-            ok = (fused || dens || dg) ? iteration_fused(all_done) : (remote ? iteration_remote(all_done) : ((n_groups > 0 && cb_groups == 0) ? iteration_pipelined(all_done) : iteration_callback(all_done, have)));
+            ok = iterate(all_done);
         }
         seconds.store(std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count());
         if (!ok) { fail(t_error); break; }
@@ -1792,8 +1693,6 @@ nphip_sampler_t* nphip_sampler_create(const nphip_settings_t* set, const nphip_m
         return nullptr;
     }
     if (!s->setup()) { s->release(); delete s; return nullptr; }
-    // (the dense Gaussian's evaluation is two kernel launches of the engine's own: always capturable — 16 steps per graph unless told otherwise)
-    s->cb_graph_steps = (s->model.kind == 2 && s->launch.graph_steps > 0) ? s->launch.graph_steps : ((s->model.dense && s->launch.graph_steps == 0) ? 16 : 0);
     s->want_pause = s->launch.start_paused != 0;
     s->manual = s->launch.manual != 0;
     if (!s->manual) s->th = std::thread([s] { s->run(); });
@@ -1828,14 +1727,14 @@ int nphip_sampler_step(nphip_sampler_t* s, uint64_t n_launches, double* kernel_m
     bool all_done = false, ok = true;
     auto t0 = std::chrono::steady_clock::now();
     for (uint64_t i = 0; i < n_launches && !all_done; ++i) {
-        ok = (s->fused || s->dens || s->dg) ? s->iteration_fused(all_done) : s->iteration_callback(all_done, s->manual_have);
+        ok = s->iterate(all_done);
         if (!ok) break;
         if (launches_done) *launches_done += 1;
     }
     s->kernel_ms_acc = nullptr;
     if (ok) ok = hip_ok(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-    if (ok && s->dg && s->fused_k > 0) ok = s->dg_check((int)((s->fused_k - 1) & 1));
-    if (ok && (s->fused || s->dens || s->dg) && s->fused_k > 0 && !all_done) ok = s->check_counters((int)((s->fused_k - 1) & 1), all_done);   // (the last launch, too)
+    if (ok && s->dense_resident() && s->fused_k > 0) ok = s->dg_check((int)((s->fused_k - 1) & 1));
+    if (ok && s->mode == Drive::in_kernel && s->fused_k > 0 && !all_done) ok = s->counters_verdict(all_done, (int)((s->fused_k - 1) & 1));   // (the last launch, too)
     if (ok && kernel_ms) {
         for (size_t i = 0; i < s->timed_launches && ok; ++i) {
             float ms = 0.f;
@@ -1898,11 +1797,10 @@ uint64_t nphip_sampler_total_draws(const nphip_sampler_t* s) { return s->T; }
 double nphip_sampler_seconds(const nphip_sampler_t* s) { return s->seconds.load(); }
 uint64_t nphip_sampler_launches(const nphip_sampler_t* s) { return s->launches.load(); }
 int nphip_sampler_host_mode(const nphip_sampler_t* s) {
-    if (s->model.dense) return s->dg ? NPHIP_HOST_MODE_RESIDENT : (s->dg_fell_back ? NPHIP_HOST_MODE_FELL_BACK : NPHIP_HOST_MODE_LAUNCH_PER_EVALUATION);
-    if (s->model.kind != 1) return NPHIP_HOST_MODE_NONE;
-    if (s->remote) return NPHIP_HOST_MODE_RESIDENT;
-    if (s->remote_fell_back) return NPHIP_HOST_MODE_FELL_BACK;
-    return (s->n_groups > 0 && s->cb_groups == 0) ? NPHIP_HOST_MODE_GROUPS : NPHIP_HOST_MODE_LAUNCH_PER_EVALUATION;
+    if (s->model.kind != 1 && !s->model.dense) return NPHIP_HOST_MODE_NONE;
+    if (s->mode == Drive::host_resident || s->mode == Drive::in_kernel) return NPHIP_HOST_MODE_RESIDENT;
+    if (s->fell_back) return NPHIP_HOST_MODE_FELL_BACK;
+    return s->mode == Drive::host_pipelined ? NPHIP_HOST_MODE_GROUPS : NPHIP_HOST_MODE_LAUNCH_PER_EVALUATION;
 }
 
 static bool read_ctl(nphip_sampler_t* s, std::vector<Ctl>& h) {
@@ -2371,6 +2269,22 @@ int nphip_test_choose_geometry(int kind, int dense, uint64_t dim, int waves_per_
     const int64_t v[9] = {g.W, (int64_t)g.family, g.kernel_nv, g.ld, g.lean, g.stream_cache, g.sig_lds, g.no_register_kernel, in_table};
     std::copy(v, v + 9, out);
     snprintf(name, 16, "%s", kFamilyNames[(int)g.family]);
+    return NPHIP_OK;
+}
+
+// Host-side test hook (no GPU involved): the plan choose_drive() gives a job (drive_plan.h).  in[16] = kind, dense, n, dim, W, ld, manual,
+// staging given, host_groups, host_persist, graph_steps, no_register_kernel, low_rank_metric, store_divergences, pause draws, CUs;
+// out[17] = mode, zero_copy, n_groups, grp_lo[9], remote_nv, persist_evals, fall_back_after, graph_steps, first sequence number.
+int nphip_test_choose_drive(const int64_t* in, int64_t* out) {
+    DriveIn d;
+    d.kind = (int)in[0]; d.dense = in[1] != 0; d.n = (uint64_t)in[2]; d.dim = (uint64_t)in[3]; d.W = (int)in[4]; d.ld = in[5]; d.manual = in[6] != 0;
+    d.staging_given = in[7] != 0; d.host_groups = (int)in[8]; d.host_persist = (int)in[9]; d.graph_steps = (int)in[10];
+    d.no_register_kernel = in[11] != 0; d.low_rank_metric = in[12] != 0; d.store_divergences = in[13] != 0; d.n_pause = (int)in[14]; d.cus = (int)in[15];
+    if (d.n == 0 || !(d.W == 1 || d.W == 2 || d.W == 4 || d.W == 8 || d.W == 16)) { set_error("choose_drive needs a chain and 1, 2, 4, 8 or 16 waves per chain (what setup() accepts)"); return NPHIP_ERR; }
+    const DrivePlan p = choose_drive(d);
+    out[0] = (int64_t)p.mode; out[1] = p.zero_copy; out[2] = p.n_groups;
+    for (int g = 0; g <= kMaxGroups; ++g) out[3 + g] = (int64_t)p.grp_lo[g];
+    out[12] = p.remote_nv; out[13] = p.persist_evals; out[14] = p.fall_back_after; out[15] = p.graph_steps; out[16] = p.seq_first;
     return NPHIP_OK;
 }
 

@@ -375,6 +375,102 @@ def test_geometry_choice_by_dimension_and_request():
             assert not bad, (kw, w, bad[:5])
 
 
+def test_drive_plan_by_model_and_request():
+    """How the host drives a job — the mode, the groups of chains, zero-copy staging, evaluations per resident launch, steps per graph — is
+    one pure function of the model and the request (csrc/drive_plan.h: choose_drive).  The rows are what the engine's set-up decided
+    before the function existed, quirks included; the sweep holds what every grouping rule must keep: at most eight groups, none of
+    them empty, covering all chains, on whole workgroups where the chains of a workgroup run as one."""
+    from nutpie_amd import _lib
+
+    def plan(dim, n, kind=1, dense=False, **kw):
+        g = _lib.test_choose_geometry(dim, kind=kind, dense=dense, low_rank_metric=kw.get("low_rank_metric", False),
+                                      no_register_kernel=kw.pop("no_register_kernel", False))
+        return _lib.test_choose_drive(n, dim, kind=kind, dense=dense, W=g["W"], ld=g["ld"], no_register_kernel=g["no_register_kernel"], **kw)
+
+    def check(p, mode, bounds=None, **want):
+        assert p["mode"] == mode, (p, mode)
+        if bounds is not None:
+            assert p["bounds"] == bounds and p["n_groups"] == max(0, len(bounds) - 1), (p, bounds)
+        for k, v in want.items():
+            assert p[k] == v, (k, v, p)
+
+    # ---- host callback, dim = 10 (one wave per chain)
+    check(plan(10, 40), "host_resident", [0, 8, 16, 24, 32, 40], persist_evals=256, zero_copy=True, seq_first=1, remote_nv=1, fall_back_after=0)
+    check(plan(10, 40, host_groups=3), "host_resident", [0, 12, 24, 40])
+    check(plan(10, 40, host_persist=3), "host_resident", persist_evals=3)
+    check(plan(10, 40, host_persist=-37), "host_resident", persist_evals=7, fall_back_after=37)
+    check(plan(10, 40, host_persist=1), "host_pipelined", [0, 20, 40], seq_first=0)
+    check(plan(10, 40, host_groups=3, host_persist=1), "host_pipelined", [0, 13, 26, 40])
+    check(plan(10, 40, host_groups=9, host_persist=1), "host_pipelined", [0, 20, 40])      # more than eight: ignored
+    check(plan(10, 256), "host_resident", list(range(0, 257, 32)))
+    check(plan(10, 1024), "host_resident", list(range(0, 1025, 128)))
+    check(plan(10, 1025), "host_pipelined", [0, 256, 512, 768, 1025])
+    check(plan(10, 2), "host_resident", [0, 2])
+    check(plan(10, 1), "host_sync", [], zero_copy=True)
+    check(plan(10, 40, manual=True), "host_sync", [], zero_copy=True)
+    check(plan(10, 40, staging_given=True), "host_sync", [], zero_copy=False)
+    check(plan(10, 40, host_groups=1), "host_sync", [], zero_copy=True)
+    for kw in (dict(low_rank_metric=True), dict(store_divergences=True), dict(no_register_kernel=True)):
+        check(plan(10, 40, **kw), "host_pipelined", [0, 20, 40])
+    # ---- host callback, wider rows
+    assert (lambda g: (g["W"], g["ld"]))(_lib.test_choose_geometry(1500, kind=1)) == (2, 1536)
+    assert (lambda g: (g["W"], g["ld"]))(_lib.test_choose_geometry(5000, kind=1)) == (4, 5120)
+    check(plan(1500, 5, host_groups=2, host_persist=256), "host_resident", [0, 2, 5], remote_nv=6)
+    check(plan(1500, 5, host_groups=2, host_persist=1), "host_pipelined", [0, 2, 5])
+    check(plan(1000, 1024, host_persist=256), "host_resident", list(range(0, 1025, 128)))
+    check(plan(1000, 1024), "host_pipelined", [0, 256, 512, 768, 1024], zero_copy=True)    # 8.19 MB: zero-copy, over the 4 MB resident limit
+    check(plan(1000, 1025), "host_sync", [], zero_copy=False)
+    check(plan(5000, 6, host_groups=2), "host_pipelined", [0, 3, 6])                      # ten chunks per wave have no resident kernel
+    # ---- device callback
+    check(plan(200, 24, kind=2, host_groups=4), "device_groups", [0, 4, 12, 16, 24], zero_copy=False)
+    check(plan(1000, 24, kind=2, host_groups=3), "device_groups", [0, 8, 16, 24])
+    check(plan(1000, 24, kind=2, host_groups=12), "device_groups", [0, 3, 6, 9, 12, 15, 18, 21, 24])   # more than eight: clamped
+    check(plan(1000, 7, kind=2, host_groups=2), "device", [])
+    check(plan(1000, 24, kind=2, host_groups=3, manual=True), "device", [])
+    check(plan(10, 40, kind=2, graph_steps=16), "device", [], graph_steps=16)
+    check(plan(10, 40, kind=2), "device", [], graph_steps=0)
+    # ---- dense Gaussian
+    dense = lambda dim, n, **kw: plan(dim, n, kind=2, dense=True, **kw)
+    for dim, n, kw in ((100, 8, {}), (37, 5, {}), (100, 1, {}), (129, 1024, {}), (257, 301, {}), (300, 70, dict(host_persist=2)),
+                       (1000, 6, dict(host_persist=2)), (1024, 130, dict(host_persist=2))):
+        check(dense(dim, n, **kw), "in_kernel", [])
+    for dim, n, kw in ((100, 8, dict(host_persist=1)), (1000, 6, {}), (1100, 6, {}), (100, 4, dict(host_groups=2)), (129, 1028, {})):
+        check(dense(dim, n, **kw), "device", [])                                           # (1028 chains: 257 workgroups on 256 CUs)
+    check(dense(100, 16, host_groups=2), "device_groups", [0, 8, 16])
+    assert [dense(100, 8, graph_steps=k)["graph_steps"] for k in (0, -1, 5)] == [16, 0, 5]
+    # ---- fused models and compiled densities: nothing to decide
+    for kind in (0, 3):
+        check(_lib.test_choose_drive(40, 10, kind=kind, host_groups=4, graph_steps=16), "in_kernel", [], zero_copy=False, graph_steps=0)
+
+    # what setup() refuses never reaches the function (a job without chains, a geometry without waves)
+    for bad in (dict(n=0, W=1), dict(n=40, W=0), dict(n=40, W=3)):
+        with pytest.raises(RuntimeError, match="choose_drive needs"):
+            _lib.test_choose_drive(bad["n"], 10, W=bad["W"])
+    # ---- sweep: every chain count and group request under each mode's preconditions, at 1, 2 and 4 waves per chain
+    shapes = {1: (10, 128), 2: (1500, 1536), 4: (3000, 3072)}    # W: (dim, ld) with a resident kernel
+    conds = (dict(kind=0), dict(kind=1, manual=True), dict(kind=1, host_persist=1), dict(kind=1), dict(kind=1, host_persist=2),
+             dict(kind=2), dict(kind=2, dense=True), dict(kind=2, dense=True, manual=True))
+    seen = set()
+    for W, (dim, ld) in shapes.items():
+        per_wg = 4 if W == 1 else 1
+        for kw in conds:
+            for hg in range(10):
+                for n in range(1, 1101):
+                    p = _lib.test_choose_drive(n, dim, W=W, ld=ld, host_groups=hg, **kw)
+                    seen.add(p["mode"])
+                    ng, lo = p["n_groups"], p["grp_lo"]
+                    assert 0 <= ng <= 8, (W, kw, hg, n, p)
+                    assert (ng > 0) == (p["mode"] in ("host_pipelined", "host_resident", "device_groups")), (W, kw, hg, n, p)
+                    if ng == 0:
+                        continue
+                    assert lo[0] == 0 and lo[ng] == n and all(lo[g] < lo[g + 1] for g in range(ng)), (W, kw, hg, n, p)
+                    if p["mode"] in ("host_resident", "device_groups"):
+                        assert all(lo[g] % per_wg == 0 for g in range(1, ng)), (W, kw, hg, n, p)
+                    if kw["kind"] == 1:
+                        assert p["zero_copy"] and not kw.get("manual"), (W, kw, hg, n, p)
+    assert seen == set(_lib.DRIVE_MODES)
+
+
 def test_sampler_constructors_do_not_drop_arguments_silently():
     """The reference's PySampler.from_pymc / from_stan / from_pyfunc take a progress type, a callback and a storage back-end
     (wrapper.rs:1189-1250).  Here progress is driven one layer up and there is no storage back-end: passing either raises."""
