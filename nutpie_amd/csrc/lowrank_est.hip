@@ -336,12 +336,17 @@ __device__ void estimate_one(const Params& P, const int slot, double* lds) {
     int bad = 0;
     for (int i = tid; i < D; i += kThreads) {
         double sx = 0.0, sg = 0.0;
+        const double x0 = X[i], g0 = Gx[i];
+        bool const_x = true, const_g = true;
         for (int t = 0; t < m; ++t) {
             const double x = X[(long long)t * P.draw_stride + i], g = Gx[(long long)t * P.draw_stride + i];
             if (!(fabs(x) < inf) || !(fabs(g) < inf)) bad = 1;
+            const_x = const_x && x == x0; const_g = const_g && g == g0;
             sx += x; sg += g;
         }
-        mean_x[i] = sx / (double)m; mean_g[i] = sg / (double)m;
+        // a coordinate that never moved (a chain whose proposals were all rejected) has ITS value as mean, exactly: the rounded sum over m
+        // misses it by an ulp, and the ratio of two such residues came out as the scaling (sigma^2 = 32, 256, ... for a constant window)
+        mean_x[i] = const_x ? x0 : sx / (double)m; mean_g[i] = const_g ? g0 : sg / (double)m;
     }
     bad = __syncthreads_or(bad);   // a window with a non-finite entry says nothing: the identity for this chain
     for (int i = tid; i < D; i += kThreads) {

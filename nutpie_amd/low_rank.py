@@ -209,12 +209,15 @@ def estimate(x, gx, gamma: float, cutoff: float, k_max: int = K_MAX, basis_draws
     # a window with a non-finite entry says nothing: that chain gets the identity (sigma = 1, no columns) instead of a NaN metric
     ok = (torch.isfinite(x).flatten(1).all(1) & torch.isfinite(gx).flatten(1).all(1))[:, None, None]
     x, gx = torch.where(ok, x, torch.zeros_like(x)), torch.where(ok, gx, torch.zeros_like(gx))
-    mean = x.mean(1)
-    sx = x.std(1, unbiased=True)
-    sg = gx.std(1, unbiased=True)
+    # a coordinate that never moved has its value as mean and no spread, exactly (the rounded mean of m equal numbers misses them by an
+    # ulp, and the ratio of two such residues would be the scaling): a constant window gives the identity
+    cx, cg = (x == x[:, :1]).all(1), (gx == gx[:, :1]).all(1)
+    mean = torch.where(cx, x[:, 0], x.mean(1))
+    sx = torch.where(cx, torch.zeros_like(mean), x.std(1, unbiased=True))
+    sg = torch.where(cg, torch.zeros_like(mean), gx.std(1, unbiased=True))
     stds = torch.sqrt(sx / sg)
     stds = torch.where(torch.isfinite(stds) & (stds > 0), stds, torch.ones_like(stds)).clamp(1e-10, 1e10)
-    gmean = gx.mean(1, keepdim=True)
+    gmean = torch.where(cg, gx[:, 0], gx.mean(1))[:, None, :]
     if basis_draws is not None and m > basis_draws:
         pick = torch.as_tensor(basis_pick(m, basis_draws), device=x.device)
         x, gx = x.index_select(1, pick), gx.index_select(1, pick)

@@ -13,14 +13,21 @@ import numpy as np
 from scipy import linalg as sla
 
 
-def estimate_chain(x, g, gamma, cutoff, k_max=16):
-    """x, g: [m, D] draws and gradients of one chain's window.  Returns (sigma2 [D], V [D, k], lam [k])."""
+def estimate_chain(x, g, gamma, cutoff, k_max=16, pick=None):
+    """x, g: [m, D] draws and gradients of one chain's window; ``pick``: the draws that span the subspace (None: all of them; the
+    moments always come from all).  Returns (sigma2 [D], V [D, k], lam [k])."""
     m, D = x.shape
-    sx, sg = x.std(0, ddof=1), g.std(0, ddof=1)
-    s = np.sqrt(sx / sg)
+    # (a coordinate that never moved: its value is the mean and its spread zero, exactly — not what rounding leaves of either)
+    cx, cg = (x == x[0]).all(0), (g == g[0]).all(0)
+    sx, sg = np.where(cx, 0.0, x.std(0, ddof=1)), np.where(cg, 0.0, g.std(0, ddof=1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s = np.sqrt(sx / sg)
     s = np.where(np.isfinite(s) & (s > 0), s, 1.0).clip(1e-10, 1e10)
-    X = (x - x.mean(0)) / s
-    G = (g - g.mean(0)) * s
+    X = (x - np.where(cx, x[0], x.mean(0))) / s
+    G = (g - np.where(cg, g[0], g.mean(0))) * s
+    if pick is not None:
+        X, G = X[np.asarray(pick)], G[np.asarray(pick)]
+        m = len(X)
     Z = np.concatenate([X, G], 0)                                # [2m, D]
     # orthonormal basis of the span of the window (rows of Z): right singular vectors with non-negligible singular values
     _, sv, Vt = np.linalg.svd(Z, full_matrices=False)

@@ -271,19 +271,24 @@ def test_native_estimator_kernel_against_the_torch_formulation_and_the_cpu_oracl
     for c in range(n):
         got = ref.dense_metric(sig2[c], V[c].T, lam[c])
         want = ref.dense_metric(s2_t[c], V_t[c].T, lam_t[c])
-        # Where the basis has full rank (2b <= D) the formulation is ill-conditioned in ANY arithmetic: the geometric mean goes through
-        # Cg^1/2 Cx Cg^1/2, whose condition number is the product of two that are 1 / gamma each — two exact-arithmetic-equal
-        # formulations evaluated with LAPACK differ by 5e-4 on these problems (the kernel works in the eigenbasis of Cg, estimate() does
-        # not; tests/test_low_rank_cpu.py allows estimate() 1e-4 against the numpy restatement for the same reason).  With a
-        # rank-deficient basis the dropped directions take the small eigenvalues with them and everything agrees to rounding.
-        tol = 1e-6 if 2 * len(pick) > D else 3e-3
-        assert np.abs(got - want).max() <= tol * np.abs(want).max(), (c, np.abs(got - want).max() / np.abs(want).max())
+        # The kernel itself is held to a 50-digit reference in tests/test_gpu_low_rank_estimator.py (2e-16 ... 8e-8 from the exact metric).
+        # What is compared HERE is estimate() on the GPU, and where the basis has full rank (2b <= D) the difference is estimate()'s own
+        # error: half Cx half has a condition number of 1 / gamma^2 and the batched eigensolver is accurate to eps |A| — measured on these
+        # windows up to 2.6e-4 (D = 173) and 1.3e-4 (D = 64), against 4e-7 of the same formulation with LAPACK on the CPU.  (This comment
+        # once read "ill-conditioned in ANY arithmetic" and the bound 3e-3: the measurement says otherwise.)  With a rank-deficient basis
+        # the dropped directions take the small eigenvalues with them: 2e-7 at the most.
+        tol = 1e-6 if 2 * len(pick) > D else 1e-3
+        diff = np.abs(got - want).max() / np.abs(want).max()
+        print("kernel against estimate() on the GPU: D %d m %d chain %d  %.2e" % (D, m, c, diff))
+        assert diff <= tol, (c, diff)
         assert k_used[c] == int((lam_t[c] != 1.0).sum()) and (lam[c][k_used[c]:] == 1.0).all() and (V[c][k_used[c]:] == 0.0).all()
         vu = V[c][:k_used[c]]
         assert np.abs(vu @ vu.T - np.eye(k_used[c])).max() < 1e-9          # orthonormal columns
         if basis is None or m <= basis:
             want2 = ref.dense_metric(*ref.estimate_chain(x[c], g[c], 1e-5, cutoff, lr.K_MAX))
-            assert np.abs(got - want2).max() <= max(10 * tol, 1e-6) * np.abs(want2).max()
+            diff2 = np.abs(got - want2).max() / np.abs(want2).max()
+            print("kernel against the numpy restatement: D %d m %d chain %d  %.2e" % (D, m, c, diff2))
+            assert diff2 <= 1e-6, (c, diff2)   # (measured: 2.2e-8 at the most, the numpy restatement's own distance from the exact metric)
     assert k_used.max() >= 1 or cutoff > 50   # (the problems have strong directions: the test is not about empty metrics)
     # a window with a non-finite entry: exactly the identity for that chain, the others untouched
     tr_x[chains[1], lo + 3, D // 2] = np.inf
