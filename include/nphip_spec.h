@@ -73,7 +73,9 @@ NPHIP_HD nphip_u32x4 nphip_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint3
     return o;
 }
 
-/* 53-bit uniform in the open interval (0,1): (k + 0.5) * 2^-53, k = top 53 bits. */
+/* 53-bit uniform: (k + 0.5) * 2^-53 rounded to double, k = top 53 bits.  The interval is (0, 1]: from k = 2^52 on, k + 0.5 is not a double and
+ * rounds to even, so the smallest value is 2^-54 and k = 2^53 - 1 (probability 2^-53 per uniform) gives 1.0.  nphip_normal_pair then has a radius
+ * of -0.0 (u1 = 1.0) or leaves the domain of nphip_sincos2pi (u2 = 1.0, see there).  Pinned by tests/test_spec_reference_cpu.py. */
 NPHIP_HD double nphip_u01(uint32_t hi, uint32_t lo) {
     uint64_t x = ((uint64_t)hi << 32) | (uint64_t)lo;
     return ((double)(x >> 11) + 0.5) * 0x1.0p-53;
@@ -90,7 +92,8 @@ NPHIP_HD uint64_t nphip_d2bits(double d) { uint64_t b; memcpy(&b, &d, 8); return
 NPHIP_HD double nphip_pow2i(int k) { return nphip_bits2d((uint64_t)(k + 1023) << 52); }
 
 /* exp(x): k = rint(x/ln2), r = x - k ln2 (Cody-Waite, fma), Taylor degree 13 in
- * Horner/fma form, scaled by 2^k in two exact steps.  <= 2 ulp. */
+ * Horner/fma form, scaled by 2^k in two exact steps.  <= 2 ulp, subnormal results and both cut-offs included (measured against a 50-digit
+ * reference at every reduction boundary (k + 1/2) ln 2, k = -1074 .. 1024: 0.86 ulp; profiles/spec_accuracy.txt). */
 /* NPHIP_K(c): a literal of the polynomial kernels.  On the device it is pinned in an SGPR pair at its point of
  * use (an empty asm the optimiser cannot move): otherwise the ~40 coefficients are hoisted out of the sampler's
  * main loop into VGPRs and spilled to scratch, and every Horner step waits on a scratch reload.  Same value,
@@ -172,7 +175,8 @@ NPHIP_HD void nphip_w_add(double m1, int64_t e1, double m2, int64_t e2, double* 
 }
 
 /* log(x): x = 2^e m, m in [sqrt(1/2), sqrt(2)); s = (m-1)/(m+1);
- * log m = 2s + s z R(z), z = s^2, R = sum_{n=1..12} 2/(2n+1) z^(n-1). <= 2 ulp. */
+ * log m = 2s + s z R(z), z = s^2, R = sum_{n=1..12} 2/(2n+1) z^(n-1). <= 2 ulp: measured 1.95 ulp at 0x1.644e12f22e5f1p-1, just below sqrt(1/2),
+ * where e = -1 cancels against log m — no margin to speak of, and tests/test_spec_reference_cpu.py holds the 2. */
 NPHIP_HD double nphip_log(double x) {
     if (x != x) return x;
     if (x < 0.0) return NAN;
@@ -204,7 +208,8 @@ NPHIP_HD double nphip_log(double x) {
     return fma(de, NPHIP_K(0x1.62e42fee00000p-1), fma(de, NPHIP_K(0x1.a39ef35793c76p-33), logm));
 }
 
-/* log(1+y) for y >= 0 (HP-15C trick). */
+/* log(1+y) for y >= 0 (HP-15C trick), meant for y in [0, 1] — what nphip_logaddexp passes.  There: 2.05 ulp at the points of tests/spec_reference.py (2.62 ulp in a
+ * wider scan), held at 4 ulp: the margin covers arguments no table holds.  Far outside, log(u) * y overflows: nphip_log1p(1e306) is inf. */
 NPHIP_HD double nphip_log1p(double y) {
     double u = 1.0 + y;
     if (u == 1.0) return y;
@@ -212,7 +217,8 @@ NPHIP_HD double nphip_log1p(double y) {
 }
 
 /* logaddexp as nuts-rs computes tree weights (restated from the crate's
- * math helpers). */
+ * math helpers).  |error| <= 8 * 2^-53 * max(1, |a|, |b|) (measured: 1.1 of these units); NOT a bound in ulp of the
+ * result: where a and the log1p term cancel (result near 0) the error reaches 100 ulp and more of it. */
 NPHIP_HD double nphip_logaddexp(double a, double b) {
     if (a == b) return a + 0x1.62e42fefa39efp-1;
     double diff = a - b;
@@ -221,7 +227,8 @@ NPHIP_HD double nphip_logaddexp(double a, double b) {
     return diff; /* NaN */
 }
 
-/* sin(2 pi u), cos(2 pi u) for u in [0,1): exact octant reduction, Taylor on [0, pi/4]. */
+/* sin(2 pi u), cos(2 pi u) for u in [0,1): exact octant reduction, Taylor on [0, pi/4].  Absolute error <= 4e-16 (measured 1.1e-16), exact at the
+ * quarter points.  u = 1.0 is outside the domain: q = 4 takes the last branch and the answer is (-1, 0), not (0, 1). */
 NPHIP_HD void nphip_sincos2pi(double u, double* sn, double* cs) {
     double t = 4.0 * u;
     double qd = floor(t);

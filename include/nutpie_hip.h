@@ -342,6 +342,15 @@ void* nphip_sampler_device_ptr(nphip_sampler_t*, const char* name);
 /* Evaluate the device implementations of include/nphip_spec.h on arrays (parity tests).
  * fn: 0 exp 1 log 2 log1p 3 sin2pi 4 cos2pi 5 sqrt 6 reciprocal 7 normals(seed=x[0],chain=x[1],draw=x[2],purpose=x[3]) */
 int nphip_test_detmath(int device, int fn, uint64_t n, const double* x, double* y);
+/* Every function of include/nphip_spec.h on records (tests/test_gpu_spec_edges.py): point i reads x[i][0 .. n_in) and writes y[i][0 .. n_out), one
+ * thread per point in one launch.  Integers (exponents, Philox words) travel as doubles.  fn (n_in -> n_out):
+ *   0 exp (1->1)   1 log (1->1)   2 log1p (1->1)   3 sincos2pi: u -> sin, cos (1->2)   4 sqrt (1->1)   5 a / b (2->1)   6 logaddexp(a, b) (2->1)
+ *   7 exp_parts: x -> p, k (1->2)   8 exp as the single leaf takes it: parts of x clamped to +-1e9, then nphip_exp_scale(x, p, k) (1->1)
+ *   9 the same through the pair path's exp_scale_select (1->1)   10 w_leaf: x -> m, e (1->2)   11 w_rel: m, e, E -> m 2^(e - E) (3->1)
+ *   12 w_add: m1, e1, m2, e2 -> m, e (4->2)   13 the merge's acceptance: u, m1, e1, m2, e2 -> u * (w1 + w2) < w2 as 1.0 or 0.0 (5->1)
+ *   14 normal_pair of four given words -> z0, z1 (4->2)   15 philox: seed lo, seed hi, c0 .. c3 -> four words (6->4)   16 u01: hi, lo -> u (2->1)
+ * A wrong (n_in, n_out) for fn is an error. */
+int nphip_test_spec(int device, int fn, uint64_t n, int n_in, const double* x, int n_out, double* y);
 /* the stages of nphip_batched_eigh on their own.  mode 1: Householder tridiagonalisation only — w = the diagonal of T, row 0 of each a = its
  * sub-diagonal (entry i couples i and i + 1); mode 2: also Q, returned in a (T = Q' A Q); mode 3: the decomposition, with w[0..6] of every
  * matrix replaced by cycle counts (tridiagonalisation, Q, QL recurrence, QL application, rotations, sweeps, total) */

@@ -199,6 +199,7 @@ def lib():
             L.nphip_sampler_device_ptr.restype = C.c_void_p
             L.nphip_sampler_device_ptr.argtypes = [C.c_void_p, C.c_char_p]
             L.nphip_test_detmath.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]
+            L.nphip_test_spec.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
             L.nphip_test_dot.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
             L.nphip_test_rowpool.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
             L.nphip_test_choose_geometry.argtypes = [C.c_int, C.c_int, C.c_uint64] + [C.c_int] * 6 + [C.POINTER(C.c_int64), C.c_char_p]
@@ -1086,6 +1087,22 @@ def test_normals(seed, chain, draw, purpose, n, device=0):
     x = np.array([seed, chain, draw, purpose], dtype=np.float64)
     y = np.empty(n)
     if lib().nphip_test_detmath(device, 7, C.c_uint64(n), x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p)) != NPHIP_OK:
+        raise RuntimeError(_err())
+    return y
+
+
+# fn -> (code, n_in, n_out) of nphip_test_spec (include/nutpie_hip.h has the table)
+SPEC_FNS = {"exp": (0, 1, 1), "log": (1, 1, 1), "log1p": (2, 1, 1), "sincos2pi": (3, 1, 2), "sqrt": (4, 1, 1), "div": (5, 2, 1), "logaddexp": (6, 2, 1),
+            "exp_parts": (7, 1, 2), "exp_scale": (8, 1, 1), "exp_scale_select": (9, 1, 1), "w_leaf": (10, 1, 2), "w_rel": (11, 3, 1), "w_add": (12, 4, 2),
+            "accept": (13, 5, 1), "normal_pair": (14, 4, 2), "philox": (15, 6, 4), "u01": (16, 2, 1)}
+
+
+def test_spec(fn: str, x, device=0):
+    """The device's ``fn`` of include/nphip_spec.h on the rows of ``x[n, n_in]`` (``x[n]`` where n_in is 1): ``y[n, n_out]``, one thread per row."""
+    code, n_in, n_out = SPEC_FNS[fn]
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n_in)
+    y = np.empty((x.shape[0], n_out))
+    if lib().nphip_test_spec(device, code, C.c_uint64(x.shape[0]), n_in, x.ctypes.data_as(C.c_void_p), n_out, y.ctypes.data_as(C.c_void_p)) != NPHIP_OK:
         raise RuntimeError(_err())
     return y
 

@@ -39,6 +39,7 @@ hipError_t launch_dense_resident(const Args* d_args, int nv, int max_evals, hipS
 hipError_t launch_dense_grad(const double* X, const double* Pp, const double* mu, double* G, double* logp, int64_t n, int64_t D, int64_t KP, int W, hipStream_t st);
 hipError_t launch_mfma_f64_rate(double* out, int blocks, int iters, hipStream_t st);
 hipError_t launch_test_detmath(int fn, uint64_t n, const double* x, double* y, hipStream_t st);
+hipError_t launch_test_spec(int fn, uint64_t n, int n_in, const double* x, int n_out, double* y, hipStream_t st);
 hipError_t launch_test_dot(int W, uint64_t n, const double* x, const double* y, double* out, hipStream_t st);
 }  // namespace nphip
 
@@ -2184,6 +2185,23 @@ int nphip_test_detmath(int device, int fn, uint64_t n, const double* x, double* 
               hip_ok(launch_test_detmath(fn, n, dx, dy, nullptr), "launch") &&
               hip_ok(hipMemcpy(y, dy, n * 8, hipMemcpyDeviceToHost), "D2H");
     (void)hipFree(dx); (void)hipFree(dy);
+    return ok ? NPHIP_OK : NPHIP_ERR;
+}
+
+int nphip_test_spec(int device, int fn, uint64_t n, int n_in, const double* x, int n_out, double* y) {
+    // (n_in, n_out) of fn 0 .. 16, the table of nutpie_hip.h: the kernel indexes its records by them, so they are checked here
+    static const int shape[17][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 2}, {1, 1}, {2, 1}, {2, 1}, {1, 2}, {1, 1}, {1, 1}, {1, 2}, {3, 1}, {4, 2}, {5, 1}, {4, 2}, {6, 4}, {2, 1}};
+    if (fn < 0 || fn > 16 || n_in != shape[fn][0] || n_out != shape[fn][1]) { set_error("nphip_test_spec: unknown fn or wrong record shape"); return NPHIP_ERR; }
+    if (n == 0) return NPHIP_OK;
+    if (n > (1ull << 24)) { set_error("nphip_test_spec: at most 2^24 points"); return NPHIP_ERR; }
+    if (hipSetDevice(device) != hipSuccess) { set_error("no HIP device"); return NPHIP_ERR; }
+    double *dx = nullptr, *dy = nullptr;
+    bool ok = hip_ok(hipMalloc((void**)&dx, n * n_in * 8), "hipMalloc") && hip_ok(hipMalloc((void**)&dy, n * n_out * 8), "hipMalloc");
+    ok = ok && hip_ok(hipMemcpy(dx, x, n * n_in * 8, hipMemcpyHostToDevice), "H2D") &&
+         hip_ok(launch_test_spec(fn, n, n_in, dx, n_out, dy, nullptr), "launch") &&
+         hip_ok(hipMemcpy(y, dy, n * n_out * 8, hipMemcpyDeviceToHost), "D2H");
+    if (dx) (void)hipFree(dx);
+    if (dy) (void)hipFree(dy);
     return ok ? NPHIP_OK : NPHIP_ERR;
 }
 

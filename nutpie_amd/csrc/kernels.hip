@@ -52,6 +52,17 @@
 
 namespace nphip {
 
+// exp(x) from its parts as nphip_exp_scale computes it, with the range cases as selects: the lanes of a pair hold different arguments
+// (at namespace scope: the pair path of the leaf and the test hook k_test_spec call this one function)
+static __device__ __forceinline__ double exp_scale_select(double x, double p, double k) {
+    const int ki = (int)k;
+    const int k1 = ki / 2, k2 = ki - k1;
+    double e = (p * nphip_pow2i(k1)) * nphip_pow2i(k2);   // (out of range: bits that the selects below replace)
+    e = x < -745.2 ? 0.0 : e;
+    e = x > 709.782712893384 ? (double)INFINITY : e;
+    return e;
+}
+
 // ----------------------------------------------------------------------------------------
 // wave / workgroup primitives
 // ----------------------------------------------------------------------------------------
@@ -2315,16 +2326,6 @@ struct Machine {
         c->prof[0] += (int64_t)__builtin_readcyclecounter() - tp0;
 #endif
     }
-    // exp(x) from its parts as nphip_exp_scale computes it, with the range cases as selects: the lanes of a pair hold different arguments
-    static __device__ __forceinline__ double exp_scale_select(double x, double p, double k) {
-        const int ki = (int)k;
-        const int k1 = ki / 2, k2 = ki - k1;
-        double e = (p * nphip_pow2i(k1)) * nphip_pow2i(k2);   // (out of range: bits that the selects below replace)
-        e = x < -745.2 ? 0.0 : e;
-        e = x > 709.782712893384 ? (double)INFINITY : e;
-        return e;
-    }
-
     // returns true when an out-of-line (rare) path ran.  pair (PAIRS only): leaf j (odd) first, then leaf j + 1 as below; *a_ended: the draw ended at leaf j.
     // (One body for both forms, the pair's first leaf a block in front of it: a second copy of the leaf in the loop of leaves makes the allocator spill.)
     __device__ __forceinline__ bool leaf_reg(RegsT& X, Hot& H, int32_t& end_code_out, const bool pair_ = false, bool* a_ended = nullptr) {
@@ -4794,6 +4795,56 @@ __global__ void k_test_detmath(int fn, uint64_t n, const double* x, double* y) {
     }
 }
 
+// Record-shaped hook: point i reads x[i][0 .. n_in) and writes y[i][0 .. n_out), one thread per point, every function of the contract
+// (nutpie_hip.h: nphip_test_spec has the table of fn, n_in, n_out; the host entry checks the record shapes before the launch).
+// Integers (exponents, Philox words) travel as doubles: all of them are below 2^53.
+__global__ void k_test_spec(int fn, uint64_t n, int n_in, const double* x, int n_out, double* y) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* a = x + i * (uint64_t)n_in;
+    double* o = y + i * (uint64_t)n_out;
+    switch (fn) {
+        case 0: o[0] = nphip_exp(a[0]); break;
+        case 1: o[0] = nphip_log(a[0]); break;
+        case 2: o[0] = nphip_log1p(a[0]); break;
+        case 3: nphip_sincos2pi(a[0], &o[0], &o[1]); break;
+        case 4: o[0] = sqrt(a[0]); break;
+        case 5: o[0] = a[0] / a[1]; break;
+        case 6: o[0] = nphip_logaddexp(a[0], a[1]); break;
+        case 7: nphip_exp_parts(a[0], &o[0], &o[1]); break;
+        case 8: case 9: {
+            // exp as the leaf computes it: the parts of the clamped argument, the range decided by the argument itself
+            // (8: nphip_exp_scale, the single leaf; 9: exp_scale_select, the pair)
+            const double xv = a[0], xc = xv > 1e9 ? 1e9 : (xv < -1e9 ? -1e9 : xv);
+            double p, k;
+            nphip_exp_parts(xc, &p, &k);
+            o[0] = fn == 8 ? nphip_exp_scale(xv, p, k) : exp_scale_select(xv, p, k);
+            break;
+        }
+        case 10: { int64_t e; nphip_w_leaf(a[0], &o[0], &e); o[1] = (double)e; break; }
+        case 11: o[0] = nphip_w_rel(a[0], (int64_t)a[1], (int64_t)a[2]); break;
+        case 12: { int64_t e; nphip_w_add(a[0], (int64_t)a[1], a[2], (int64_t)a[3], &o[0], &e); o[1] = (double)e; break; }
+        case 13: {   // the merge's acceptance: u * w_total < w_other with total = (m1, e1) + (m2, e2), other = (m2, e2)
+            double sm; int64_t se;
+            nphip_w_add(a[1], (int64_t)a[2], a[3], (int64_t)a[4], &sm, &se);
+            o[0] = a[0] * sm < nphip_w_rel(a[3], (int64_t)a[4], se) ? 1.0 : 0.0;
+            break;
+        }
+        case 14: {
+            nphip_u32x4 r = {{(uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2], (uint32_t)a[3]}};
+            nphip_normal_pair(r, &o[0], &o[1]);
+            break;
+        }
+        case 15: {
+            const uint64_t seed = ((uint64_t)(uint32_t)a[1] << 32) | (uint64_t)(uint32_t)a[0];
+            nphip_u32x4 r = nphip_philox(seed, (uint32_t)a[2], (uint32_t)a[3], (uint32_t)a[4], (uint32_t)a[5]);
+            for (int j = 0; j < 4; ++j) o[j] = (double)r.v[j];
+            break;
+        }
+        default: o[0] = nphip_u01((uint32_t)a[0], (uint32_t)a[1]); break;
+    }
+}
+
 template <int W>
 __global__ void k_test_dot(uint64_t n, const double* x, const double* y, double* out) {
     __shared__ double red_[8 * W];
@@ -4815,6 +4866,11 @@ __global__ void k_test_dot(uint64_t n, const double* x, const double* y, double*
 hipError_t launch_test_detmath(int fn, uint64_t n, const double* x, double* y, hipStream_t st) {
     uint64_t work = (fn == 7) ? (n + 1) / 2 : n;
     hipLaunchKernelGGL(k_test_detmath, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, fn, n, x, y);
+    return hipGetLastError();
+}
+
+hipError_t launch_test_spec(int fn, uint64_t n, int n_in, const double* x, int n_out, double* y, hipStream_t st) {
+    hipLaunchKernelGGL(k_test_spec, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fn, n, n_in, x, n_out, y);
     return hipGetLastError();
 }
 

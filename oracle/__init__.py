@@ -366,6 +366,23 @@ def logaddexp(a, b):
     return lib().oracle_logaddexp(a, b)
 
 
+# fn -> (code, n_in, n_out) of oracle_spec: the table of the engine's nphip_test_spec (include/nutpie_hip.h), restated here because nothing under
+# oracle/ imports the product
+SPEC_FNS = {"exp": (0, 1, 1), "log": (1, 1, 1), "log1p": (2, 1, 1), "sincos2pi": (3, 1, 2), "sqrt": (4, 1, 1), "div": (5, 2, 1), "logaddexp": (6, 2, 1),
+            "exp_parts": (7, 1, 2), "exp_scale": (8, 1, 1), "exp_scale_select": (9, 1, 1), "w_leaf": (10, 1, 2), "w_rel": (11, 3, 1), "w_add": (12, 4, 2),
+            "accept": (13, 5, 1), "normal_pair": (14, 4, 2), "philox": (15, 6, 4), "u01": (16, 2, 1)}
+
+
+def spec(fn: str, x):
+    """The restatement's ``fn`` of the contract on the rows of ``x[n, n_in]``: ``y[n, n_out]`` (integers travel as doubles)."""
+    code, n_in, n_out = SPEC_FNS[fn]
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, n_in)
+    y = np.empty((x.shape[0], n_out))
+    if lib().oracle_spec(code, C.c_uint64(x.shape[0]), n_in, _p(x), n_out, _p(y)) != 0:
+        raise ValueError("oracle_spec: unknown fn or wrong record shape")
+    return y
+
+
 def w_leaf(neg_energy_error):
     """Extended-range weight (m, e) of a leaf: m * 2**e ~= exp(neg_energy_error)."""
     m, e = C.c_double(), C.c_int64()

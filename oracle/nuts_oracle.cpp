@@ -1222,6 +1222,59 @@ void oracle_detmath(int fn, uint64_t n, const double* x, double* y) {
 
 double oracle_logaddexp(double a, double b) { return det_logaddexp(a, b); }
 
+// Every function of the contract on records, with the fn codes and record shapes of the engine's nphip_test_spec (include/nutpie_hip.h):
+// point i reads x[i][0 .. n_in) and writes y[i][0 .. n_out).  Returns 0, or -1 for an unknown fn or a wrong record shape.
+int oracle_spec(int fn, uint64_t n, int n_in, const double* x, int n_out, double* y) {
+    static const int shape[17][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 2}, {1, 1}, {2, 1}, {2, 1}, {1, 2}, {1, 1}, {1, 1}, {1, 2}, {3, 1}, {4, 2}, {5, 1}, {4, 2}, {6, 4}, {2, 1}};
+    if (fn < 0 || fn > 16 || n_in != shape[fn][0] || n_out != shape[fn][1]) return -1;
+    for (uint64_t i = 0; i < n; ++i) {
+        const double* a = x + i * (uint64_t)n_in;
+        double* o = y + i * (uint64_t)n_out;
+        switch (fn) {
+            case 0: o[0] = det_exp(a[0]); break;
+            case 1: o[0] = det_log(a[0]); break;
+            case 2: o[0] = det_log1p(a[0]); break;
+            case 3: det_sincos2pi(a[0], &o[0], &o[1]); break;
+            case 4: o[0] = std::sqrt(a[0]); break;
+            case 5: o[0] = a[0] / a[1]; break;
+            case 6: o[0] = det_logaddexp(a[0], a[1]); break;
+            case 7: det_exp_parts(a[0], &o[0], &o[1]); break;
+            case 8: case 9: {
+                // exp as the leaf takes it (the engine has two forms of the scaling, the oracle one): the parts of the argument clamped to
+                // +-1e9, the range decided by the argument itself; a NaN comes out of the parts
+                const double xv = a[0];
+                double p, k;
+                det_exp_parts(std::min(std::max(xv, -1e9), 1e9), &p, &k);
+                if (xv > 709.782712893384) o[0] = INFINITY;
+                else if (xv < -745.2) o[0] = 0.0;
+                else if (std::isnan(xv)) o[0] = p;
+                else { const int ki = (int)k, k1 = ki / 2, k2 = ki - k1; o[0] = (p * std::ldexp(1.0, k1)) * std::ldexp(1.0, k2); }
+                break;
+            }
+            case 10: { Weight w = w_leaf(a[0]); o[0] = w.m; o[1] = (double)w.e; break; }
+            case 11: { Weight w; w.m = a[0]; w.e = (int64_t)a[1]; o[0] = w_rel(w, (int64_t)a[2]); break; }
+            case 12: {
+                Weight u, v; u.m = a[0]; u.e = (int64_t)a[1]; v.m = a[2]; v.e = (int64_t)a[3];
+                Weight w = w_add(u, v); o[0] = w.m; o[1] = (double)w.e; break;
+            }
+            case 13: {   // a sub-tree's merge (Tree::merge_into with !is_main): u * sum.m < w_rel(other, sum.e)
+                Weight u, v; u.m = a[1]; u.e = (int64_t)a[2]; v.m = a[3]; v.e = (int64_t)a[4];
+                const Weight sum = w_add(u, v);
+                o[0] = a[0] * sum.m < w_rel(v, sum.e) ? 1.0 : 0.0; break;
+            }
+            case 14: { U4 r; for (int j = 0; j < 4; ++j) r.v[j] = (uint32_t)a[j]; normal_pair(r, &o[0], &o[1]); break; }
+            case 15: {
+                const uint64_t seed = ((uint64_t)(uint32_t)a[1] << 32) | (uint64_t)(uint32_t)a[0];
+                U4 r = philox(seed, (uint32_t)a[2], (uint32_t)a[3], (uint32_t)a[4], (uint32_t)a[5]);
+                for (int j = 0; j < 4; ++j) o[j] = (double)r.v[j];
+                break;
+            }
+            default: o[0] = u01((uint32_t)a[0], (uint32_t)a[1]); break;
+        }
+    }
+    return 0;
+}
+
 // extended-range tree weights (unit hooks)
 void oracle_w_leaf(double neg_energy_error, double* m, int64_t* e) { Weight w = w_leaf(neg_energy_error); *m = w.m; *e = w.e; }
 void oracle_w_add(double m1, int64_t e1, double m2, int64_t e2, double* m, int64_t* e) {

@@ -197,6 +197,9 @@ void oracle_set_variant(int min_refresh, int search_mode, int late_sym, int last
 void oracle_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out[4]);
 void oracle_detmath(int fn, uint64_t n, const double* x, double* y); /* 0 exp 1 log 2 log1p 3 sin2pi 4 cos2pi */
 double oracle_logaddexp(double a, double b);
+/* every function of the contract on records x[n][n_in] -> y[n][n_out]: the fn codes and record shapes of nphip_test_spec (include/nutpie_hip.h: exp_parts,
+ * w_rel, logaddexp, the normal pair of four given words, Philox words, ...); 0, or -1 for an unknown fn or a wrong shape */
+int oracle_spec(int fn, uint64_t n, int n_in, const double* x, int n_out, double* y);
 void oracle_w_leaf(double neg_energy_error, double* m, int64_t* e);
 void oracle_w_add(double m1, int64_t e1, double m2, int64_t e2, double* m, int64_t* e);
 void oracle_normals(uint64_t seed, uint32_t chain, uint32_t draw, uint32_t purpose, uint64_t n, double* out);
