@@ -332,6 +332,19 @@ int nphip_low_rank_estimate(uint64_t n, uint64_t dim, uint64_t m, uint64_t n_pic
                             int64_t chain_stride, int64_t draw_stride, const int64_t* chains_device, double gamma, double cutoff, uint64_t k_max,
                             double* sigma2, double* V, double* lambda, int32_t* k_used, double* scratch, uint64_t max_workgroups, void* stream);
 
+/* The same estimator for the shapes above: 1 <= dim <= 1024, 2 <= m, 1 <= n_pick <= 64, n_pick <= m, n_pick <= dim, 1 <= k_max <= 16 — a
+ * subspace problem of order 128 (nutpie_amd/csrc/lowrank_est_wide.hip; the shapes of nphip_low_rank_estimate are inside these limits and
+ * are accepted too).  Arguments, outputs and semantics are those of nphip_low_rank_estimate; a chain's result is a fixed function of its
+ * window and the settings, whatever the batch, the grid, the chain list or the strides.  One workgroup of 1024 threads per chain (or per
+ * several chains in turn) with ONE 128 x 128 matrix in LDS; the others are parked in the workgroup's block of `scratch`, which holds
+ *   W * 54272 + n * 16  doubles of device memory,  W = max_workgroups if 0 < max_workgroups < n, else n
+ * (per workgroup: three per-dimension vectors of 1024, three 128 x 128 matrices, 16 columns of 128; then 16 diagnostic words per chain,
+ * written by chains that are not the identity: [0], [1] the sweeps of the two Jacobi passes, [2] the rank of the basis, [3 .. 9] cycles). */
+int nphip_low_rank_estimate_wide_supported(uint64_t dim, uint64_t m, uint64_t n_pick, uint64_t k_max);
+int nphip_low_rank_estimate_wide(uint64_t n, uint64_t dim, uint64_t m, uint64_t n_pick, const int32_t* pick, const double* draws, const double* grads,
+                                 int64_t chain_stride, int64_t draw_stride, const int64_t* chains_device, double gamma, double cutoff, uint64_t k_max,
+                                 double* sigma2, double* V, double* lambda, int32_t* k_used, double* scratch, uint64_t max_workgroups, void* stream);
+
 /* Developer aid: per-section cycle counters summed over chains; all zero unless the library was built
  * with -DNPHIP_PROFILE.  [0] leapfrog cycles [1] tree cycles (hot) [2] draw-end cycles [3..5] their counts. */
 int nphip_sampler_profile(nphip_sampler_t*, int64_t out[16]);

@@ -13,10 +13,12 @@ kernels apply ``v = M^-1 p`` in the leapfrog, draw ``p ~ N(0, M)`` and carry the
 compared bit for bit, tests/test_gpu_low_rank.py) — for EVERY model flavour: fused, raw C callbacks, BridgeStan, device
 callbacks, runtime-compiled densities.  The DRIVER of the adaptation is here: chains stop between two draws at the window
 boundaries (``nphip_settings_set_pause_draws``), every stopped chain's ``(sigma^2, V, lambda)`` is estimated from the window's
-draws and gradients — round 6: by ONE kernel below the C-ABI (``nphip_low_rank_estimate``, nutpie_amd/csrc/lowrank_est.hip: a
-workgroup per chain, straight out of the engine's trace) for models of up to 256 dimensions; above that by :func:`estimate`,
-the torch formulation the kernel restates (batched eigendecompositions on the engine's ``nphip_batched_eigh`` up to order 64,
-rocSOLVER above) —, on a worker thread while the other chains run, and handed to the engine (``nphip_sampler_set_metric``);
+draws and gradients — by ONE kernel below the C-ABI, a workgroup per chain, straight out of the engine's trace:
+``nphip_low_rank_estimate`` (nutpie_amd/csrc/lowrank_est.hip: up to 512 dimensions, at most 32 basis draws — what
+:func:`basis_draws_for` takes up to 256 dimensions) or ``nphip_low_rank_estimate_wide`` (nutpie_amd/csrc/lowrank_est_wide.hip: up to
+1024 dimensions, at most 64 basis draws — every model above 256 dimensions that can be a compiled density); above 1024 dimensions
+by :func:`estimate`, the torch formulation the kernels restate (batched eigendecompositions on the engine's ``nphip_batched_eigh``
+up to order 64, rocSOLVER above) —, on a worker thread while the other chains run, and handed to the engine (``nphip_sampler_set_metric``);
 the chains go on from where they are, through a new step-size search, as nuts-rs does when the mass matrix changes.  A chain
 that needs no low-rank part and still adapts its own diagonal is released unchanged (``nphip_sampler_release``).  The estimator follows the published description (Seyboldt et al., "Preconditioning Hamiltonian Monte
 Carlo by minimizing Fisher divergence"); the crate is not in the tree — PARITY UNPINNED, like the rest of the sampler.
@@ -313,15 +315,18 @@ def torch_index(mask, like):
     return torch.as_tensor(np.nonzero(mask)[0], device=like.device)
 
 
-NATIVE_ESTIMATOR = True   # the estimator as one kernel below the C-ABI (nphip_low_rank_estimate) wherever it covers the shape
+NATIVE_ESTIMATOR = True   # the estimator as one kernel below the C-ABI (nphip_low_rank_estimate, nphip_low_rank_estimate_wide) wherever one covers the shape:
+                          # the wide kernel against estimate() on one box, 64 basis draws, D = 300 .. 1000, 1 / 64 / 256 chains per hand-in: 4.2 .. 4.6 / 4.4 .. 4.9 /
+                          # 4.9 .. 5.5 ms against 9.8 .. 10.2 / 14.4 .. 14.9 / 25.5 .. 27.9 (profiles/low_rank_estimator_wide.txt) — no batch size at which it loses
 
 
 def estimate_window(draws, grads, chains, lo: int, hi: int, gamma: float, cutoff: float, k_max: int = K_MAX, basis_draws: int | None = None,
                     max_workgroups: int = 0):
     """(sigma^2 [n, D], V rows [n, k_max, D], lambda [n, k_max]) of ``chains`` (indices, or None for all) from the window
     ``[lo, hi)`` of the trace arrays ``draws`` / ``grads`` ``[n_all, T, D]`` — :func:`estimate` + :func:`metric_of`, computed by the engine's
-    own kernel (``nphip_low_rank_estimate``: one workgroup per chain, nothing copied out of the trace, one launch) where that covers
-    the shape: up to 512 dimensions with at most 32 basis draws."""
+    own kernels (one workgroup per chain, nothing copied out of the trace, one launch) where they cover the shape:
+    ``nphip_low_rank_estimate`` up to 512 dimensions with at most 32 basis draws, ``nphip_low_rank_estimate_wide`` beyond that up to
+    1024 dimensions with at most 64 basis draws; :func:`estimate` (torch) for everything else."""
     import torch
 
     D, m = int(draws.shape[2]), int(hi) - int(lo)
@@ -332,6 +337,10 @@ def estimate_window(draws, grads, chains, lo: int, hi: int, gamma: float, cutoff
         if _lib.low_rank_estimate_supported(D, m, len(pick), k_max):
             idx = None if chains is None else torch.as_tensor(np.asarray(chains, dtype=np.int64), device=draws.device)
             sig2, V, lam, _ = _lib.low_rank_estimate(draws, grads, idx, lo, hi, pick, gamma, cutoff, k_max, max_workgroups)
+            return sig2, V, lam
+        if _lib.low_rank_estimate_wide_supported(D, m, len(pick), k_max):
+            idx = None if chains is None else torch.as_tensor(np.asarray(chains, dtype=np.int64), device=draws.device)
+            sig2, V, lam, _ = _lib.low_rank_estimate_wide(draws, grads, idx, lo, hi, pick, gamma, cutoff, k_max, max_workgroups)
             return sig2, V, lam
     if chains is None:
         x, g = draws[:, lo:hi], grads[:, lo:hi]
@@ -496,15 +505,18 @@ class LowRankSampler:
                         job = pool.submit(self._estimate, grp, self._chain_next[grp].copy())
 
     def _native_estimator(self):
-        """Whether this job's windows go to ``nphip_low_rank_estimate`` (a GPU trace of a shape the kernel covers)."""
+        """Whether this job's windows go to ``nphip_low_rank_estimate`` or ``nphip_low_rank_estimate_wide`` (a GPU trace of a shape one
+        of the two kernels covers: up to 1024 dimensions)."""
         try:
             import torch
 
             from nutpie_amd import _lib
 
             D = int(self._inner.dim)
+            b = min(basis_draws_for(D), D)
             return bool(NATIVE_ESTIMATOR and torch.cuda.is_available() and hasattr(self._inner, "device_ptr") and
-                        _lib.low_rank_estimate_supported(D, WINDOW_MAX, min(basis_draws_for(D), D), K_MAX) and basis_draws_for(D) <= 32)
+                        ((_lib.low_rank_estimate_supported(D, WINDOW_MAX, b, K_MAX) and basis_draws_for(D) <= 32) or
+                         _lib.low_rank_estimate_wide_supported(D, WINDOW_MAX, b, K_MAX)))
         except Exception:  # noqa: BLE001 - (a stand-in engine of the CPU tests)
             return False
 
