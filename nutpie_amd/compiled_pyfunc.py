@@ -401,7 +401,8 @@ def autograd_logp(density_fn: Callable) -> Callable:
     return logp
 
 
-def from_torch_density(ndim: int, density_fn: Callable, *, compile: Any = "auto", batched: bool = True, waves_per_chain: int | None = None, **kwargs):
+def from_torch_density(ndim: int, density_fn: Callable, *, compile: Any = "auto", batched: bool = True, waves_per_chain: int | None = None,
+                       wide_matrices: bool = False, **kwargs):
     """A model from a torch log-density alone: ``density_fn(x: Tensor[chains, ndim], **shared_data) -> Tensor[chains]``.
 
     ``compile`` (default ``"auto"``): the function is TRACED once (:mod:`nutpie_amd.torch_trace`: ``torch.fx`` -> the front-end's
@@ -409,7 +410,8 @@ def from_torch_density(ndim: int, density_fn: Callable, *, compile: Any = "auto"
     call, no kernel launch and no memory round trip per gradient evaluation (the reference compiles a model's logp graph likewise,
     ``python/nutpie/compile_pymc.py:668-871``).  ``"auto"`` falls back to the eager path below when the function uses an operation
     the tracer cannot map (a ``UserWarning`` names it); ``True`` raises :class:`nutpie_amd.torch_trace.UnsupportedTorchOp` instead;
-    ``False`` never traces.  ``batched=False``: ``density_fn(x: Tensor[ndim]) -> scalar`` (compiled path only).
+    ``False`` never traces.  ``batched=False``: ``density_fn(x: Tensor[ndim]) -> scalar`` (compiled path only).  ``wide_matrices``: the
+    compiled path factors traced matrices of up to 128 x 128 (``Model.compile(wide_matrices=True)``) instead of up to 32 x 32.
 
     The eager path: a batched device callback, the gradient from ``torch.autograd`` (``use_graph=True`` replays the whole evaluation
     from a HIP graph).  Keyword arguments as :func:`from_torchfunc`; ``shared_data`` entries are passed to ``density_fn`` as keyword
@@ -420,7 +422,7 @@ def from_torch_density(ndim: int, density_fn: Callable, *, compile: Any = "auto"
         from nutpie_amd.torch_trace import UnsupportedTorchOp, traced_model
 
         try:
-            return traced_model(ndim, density_fn, batched=batched, waves_per_chain=waves_per_chain,
+            return traced_model(ndim, density_fn, batched=batched, waves_per_chain=waves_per_chain, wide_matrices=wide_matrices,
                                 **{k: v for k, v in kwargs.items() if k not in ("use_graph", "expand_device_fn")})
         except (UnsupportedTorchOp, NotImplementedError, ValueError, RuntimeError) as e:
             # "auto": whatever keeps the function from becoming a resident kernel — an operation the tracer cannot map, a derivative the IR

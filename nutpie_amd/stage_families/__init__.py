@@ -27,6 +27,10 @@ def _declines(*_):
     return NotImplemented
 
 
+def _own_header(nodes):
+    return None
+
+
 @dataclasses.dataclass(frozen=True)
 class Family:
     name: str
@@ -45,9 +49,16 @@ class Family:
     adjoint: dict[str, Callable]
     #: what ``gradient`` says of an op or reader without a rule
     refusal: str
-    #: ``check(nodes, waves_per_chain) -> waves_per_chain``: the family's limits on the model's stage nodes (a ``ValueError``), and the waves
-    #: per chain it forces (returned; otherwise the argument)
+    #: ``check(nodes, waves_per_chain, **options) -> waves_per_chain``: the family's limits on the model's stage nodes (a ``ValueError``),
+    #: and the waves per chain it forces (returned; otherwise the argument)
     check: Callable = _no_limit
+    #: the keywords of ``Model.compile`` that ``check`` is given by name (a switch that belongs to the family)
+    options: tuple[str, ...] = ()
+    #: further headers of ``csrc/`` with routines of the family (hashed into a library's cache key when the source includes them) ...
+    more_headers: tuple[str, ...] = ()
+    #: ... and ``includes(nodes) -> [header] | None``: which of ``header`` and ``more_headers`` a source with these stage nodes includes
+    #: (None: ``header``)
+    includes: Callable = _own_header
     #: ops that read a stored stage result element-wise, in the loop over their own dimension
     readers: tuple[str, ...] = ()
     #: ... and the other chain headers that header includes (hashed with it into a library's cache key)
@@ -62,8 +73,9 @@ class Family:
     section: Callable = _nothing
     #: ``series_lengths(payload) -> set[int]``: lengths of the dimensions a stage's series live on (their loops are unrolled alike whatever the length)
     series_lengths: Callable = _no_lengths
-    #: results may be too long for the LDS of the generated expand function (``Model._finish`` then checks, and expands on the host)
-    long_results: bool = True
+    #: results may be too long for the LDS of the generated expand function (``Model._finish`` then checks, and expands on the host);
+    #: or ``long_results(node) -> bool``: which of the family's stages are
+    long_results: bool | Callable = True
     #: base name of a torch op (``cumsum``, ``linalg_cholesky``, the family's own ``nutpie_amd::`` custom ops) -> ``rule(c)``: the lowering
     #: the torch tracer asks BEFORE its own table, the families in table order.  ``c`` is the tracer's rule context (``c.it`` the
     #: interpreter, ``c.args`` / ``c.kwargs`` the node's evaluated arguments, ``c.name`` / ``c.base`` the op's names); a rule returns the
@@ -103,5 +115,12 @@ def family_of(op: str) -> Family | None:
 
 def chain_headers(source: str) -> list[str]:
     """the chain headers a generated source compiles with, in the order a library's cache key hashes them: for every family whose
-    ``#include`` line is in ``source``, its header and then the headers that one includes"""
-    return [h for f in FAMILIES if f'#include "{f.header}"' in source for h in (f.header,) + f.header_deps]
+    ``#include`` line is in ``source``, its header and then the headers that one includes; then the families' further headers"""
+    return ([h for f in FAMILIES if f'#include "{f.header}"' in source for h in (f.header,) + f.header_deps]
+            + [h for f in FAMILIES for h in f.more_headers if f'#include "{h}"' in source])
+
+
+def has_long_results(n) -> bool:
+    """a stage node whose result may not fit the LDS of the generated expand function (``Family.long_results``)"""
+    long = family_of(n.op).long_results
+    return bool(long(n)) if callable(long) else bool(long)

@@ -2,7 +2,11 @@
 
 K x K (K <= 32) and K x N values, row-major on a fixed-size dimension (a ``Model.product``), that one device routine turns into another
 between two loops.  ``chol`` / ``trsv`` are the user's; the other three are the adjoints the gradient emits.  payload = (K, N): N the
-columns of the right-hand sides (K for the K x K stages)."""
+columns of the right-hand sides (K for the K x K stages).
+
+Past 32 x 32, up to 128 x 128, the same ops run on the panel routines of ``csrc/wide_chain_linalg.h`` (``nphip_lw::``) when the model is
+compiled with ``wide_matrices=True`` — the family's option, handed to ``_check``; ``_call`` and ``_includes`` go by the stage's K.  The
+diagonal of such a factor is read through a gather (``_diagonal``), not element by element."""
 
 from __future__ import annotations
 
@@ -16,6 +20,8 @@ from nutpie_amd.trace_values import UnsupportedTorchOp, _is_traced, _numel, _Sym
 
 _MATOPS = ("chol", "trsv", "trsv_t", "trsv_gl", "chol_adj")
 MAX_MATRIX = 32     # the largest K a compiled density factors (8 KB per matrix and chain)
+MAX_WIDE = 128      # ... with Model.compile(wide_matrices=True): the panel routines of csrc/wide_chain_linalg.h (128 KB per matrix and chain)
+WIDE_HEADER = "wide_chain_linalg.h"
 
 
 def _side(e: Expr, what: str) -> int:
@@ -47,9 +53,28 @@ def solve_lower(L, B) -> Expr:
     return Expr("trsv", (L, B), B.dim, (k, B.dim.size // k))
 
 
+def _diagonal(L: Expr, k: int) -> Expr:
+    """``diag(L)`` of a wide matrix as a value on a K-long dimension: a gather through the index ``i (K + 1)``, read in the loop over that
+    dimension — and its adjoint a segment sum written by the loop over the K x K one: no line of source per element or row.  The index is
+    registered once per matrix dimension with the model that declared it (its name holds a double underscore, which no user data can)."""
+    kk = L.dim
+    m = kk._model() if kk._model is not None else None
+    if m is None:
+        raise ValueError("the diagonal of a wide matrix: its dimension belongs to no Model")
+    name = f"{kk.name}__diag"
+    ix = m._indices.get(name)
+    if ix is None:
+        d = kk.factors[0] if kk.factors is not None and kk.factors[0].size == k else m.dim(f"{kk.name}_diag", k)
+        ix = m._add_index(name, np.arange(k) * (k + 1), d.name, kk.name)
+    return L[ix]
+
+
 def log_det_chol(L) -> Expr:
     """``sum(log(diag(L)))``: half the log-determinant of ``L L^T``."""
+    L = Expr.wrap(L)
     k = _side(L, "log_det_chol")
+    if k > MAX_MATRIX:
+        return log(_diagonal(L, k)).sum()
     total = None
     for i in range(k):
         t = log(elem(L, i * k + i))
@@ -88,6 +113,13 @@ def lkj_corr_cholesky_lpdf(L, eta: float) -> Expr:
     L = Expr.wrap(L)
     k = _side(L, "lkj_corr_cholesky_lpdf")
     total = Expr.const(_lkj_log_norm(float(eta), k))
+    if k > MAX_MATRIX:      # the exponents as data on the diagonal's dimension (row 0 has none)
+        diag = _diagonal(L, k)
+        m = diag.dim._model()
+        name = f"{L.dim.name}__lkj{sum(1 for f in m._data if f.startswith(L.dim.name + '__lkj'))}"
+        m._data[name] = np.array([0.0] + [k - i - 1 + 2.0 * float(eta) - 2.0 for i in range(1, k)])
+        m._data_fields.append((name, "double", diag.dim))
+        return total + (Expr("data", (), diag.dim, name) * log(diag)).sum()
     for i in range(1, k):
         total = total + (k - i - 1 + 2.0 * float(eta) - 2.0) * log(elem(L, i * k + i))
     return total
@@ -173,14 +205,34 @@ def _call(gen, n: Expr) -> str:
     out = gen.store_name[n.id]
     fn = {"chol": f"cholesky<{k}>", "trsv": f"solve_lower<{k}, {m}>", "trsv_t": f"solve_lower_t<{k}, {m}, {m}, 1>",
           "trsv_gl": f"solve_lower_adj_l<{k}, {m}>", "chol_adj": f"cholesky_adj<{k}>"}[n.op]
-    return f"    nphip_la::{fn}({args}, {out}, lane);"
+    return f"    {'nphip_lw' if _is_wide(n) else 'nphip_la'}::{fn}({args}, {out}, lane);"
 
 
-def _check(nodes, waves_per_chain):
-    # one wavefront per chain runs the matrix stages
+def _is_wide(n: Expr) -> bool:
+    """a stage of a matrix past the narrow routines' limit: the panel routines run it (``_check`` has let it pass)"""
+    return n.payload[0] > MAX_MATRIX
+
+
+def _section(n: Expr):
+    """``Model.profile`` times the wide stages one by one (the narrow ones stay inside their level's section, as they were)"""
+    return f"{n.op}<{n.payload[0]}, {n.payload[1]}>" if _is_wide(n) else None
+
+
+def _includes(nodes) -> list[str]:
+    wide = [_is_wide(n) for n in nodes]
+    return (["chain_linalg.h"] if not all(wide) else []) + ([WIDE_HEADER] if any(wide) else [])
+
+
+def _check(nodes, waves_per_chain, wide_matrices=False):
     k = max(n.payload[0] for n in nodes)
-    if k > MAX_MATRIX:
-        raise ValueError(f"a compiled density factors matrices of up to {MAX_MATRIX} x {MAX_MATRIX} (this model: {k} x {k})")
+    if not wide_matrices and k > MAX_MATRIX:
+        raise ValueError(f"a compiled density factors matrices of up to {MAX_MATRIX} x {MAX_MATRIX} (this model: {k} x {k}); "
+                         f"compile(wide_matrices=True) factors up to {MAX_WIDE} x {MAX_WIDE}")
+    if k > MAX_WIDE:
+        raise ValueError(f"a compiled density with wide_matrices=True factors matrices of up to {MAX_WIDE} x {MAX_WIDE} (this model: {k} x {k})")
+    if all(_is_wide(n) for n in nodes):
+        return waves_per_chain      # the panel routines run on all the chain's waves
+    # one wavefront per chain runs the narrow matrix stages
     if waves_per_chain not in (None, 1):
         raise ValueError("a model with matrix stages (cholesky / solve_lower) runs with waves_per_chain=1")
     return 1
@@ -196,10 +248,15 @@ def _matrix(it, v, what: str) -> tuple[_Sym, int]:
     return _Sym(_bcast(v.expr, it.dim(k * k)), v.shape), k
 
 
+def _traced_limit(it) -> int:
+    """the largest traced matrix: ``trace(..., wide_matrices=True)`` sets the interpreter's ``wide_matrices``"""
+    return MAX_WIDE if getattr(it, "wide_matrices", False) else MAX_MATRIX
+
+
 def _cholesky(it, a) -> _Sym:
     A, k = _matrix(it, a, "cholesky")
-    if k > MAX_MATRIX:
-        raise UnsupportedTorchOp(f"cholesky of a {k} x {k} traced matrix (compiled densities factor up to {MAX_MATRIX} x {MAX_MATRIX})")
+    if k > _traced_limit(it):
+        raise UnsupportedTorchOp(f"cholesky of a {k} x {k} traced matrix (compiled densities factor up to {_traced_limit(it)} x {_traced_limit(it)})")
     return _Sym(cholesky(A.expr), A.shape)
 
 
@@ -214,8 +271,8 @@ def _solve_triangular(it, a, b, upper: bool, left: bool) -> _Sym:
         br = it.move(it.sym(b), lambda t: t.flip(-2))
         return it.move(_solve_triangular(it, ar, br, False, True), lambda t: t.flip(-2))
     A, k = _matrix(it, a, "solve_triangular")
-    if k > MAX_MATRIX:
-        raise UnsupportedTorchOp(f"solve_triangular with a {k} x {k} traced matrix (compiled densities solve up to {MAX_MATRIX} x {MAX_MATRIX})")
+    if k > _traced_limit(it):
+        raise UnsupportedTorchOp(f"solve_triangular with a {k} x {k} traced matrix (compiled densities solve up to {_traced_limit(it)} x {_traced_limit(it)})")
     B = it.sym(b)
     if len(B.shape) < 2 or B.shape[-2] != k:
         raise UnsupportedTorchOp(f"solve_triangular: right-hand sides of shape {B.shape} for a {k} x {k} matrix")
@@ -252,6 +309,7 @@ def _torch_solve_triangular(c):
 
 FAMILY = Family(name="linalg", ops=_MATOPS, header="chain_linalg.h", call=_call, numpy=_numpy,
                 adjoint={"chol": _chol_adjoint, "trsv": _trsv_adjoint}, refusal="second derivatives of the matrix and scan stages",
-                check=_check, long_results=False,
+                check=_check, options=("wide_matrices",), more_headers=(WIDE_HEADER,), includes=_includes, long_results=_is_wide,
+                section=_section,
                 torch_rules={"linalg_cholesky_ex": _torch_cholesky, "linalg_cholesky": _torch_cholesky, "cholesky": _torch_cholesky,
                              "linalg_solve_triangular": _torch_solve_triangular})

@@ -96,7 +96,7 @@ _UNROLL = 4   # iterations of a loop whose reads are issued together (a lone wav
 from nutpie_amd.expr import (_HALF_LOG_2PI, _UNARY_FOLD, Dim, Expr, Index, _bcast, _binary, _digamma_py, _dim_len, _join, _join3,  # noqa: F401
                              _segsum, _topo, _unary, absolute, atan, cos, digamma, elem, erf, erfc, exp, expm1, lgamma, log, log1p, pad,
                              select, sigmoid, sign, sin, softplus, sqrt, stack, tanh, trunc, where_lt)
-from nutpie_amd.stage_families import _READERS, _STAGES, FAMILIES, family_of
+from nutpie_amd.stage_families import _READERS, _STAGES, FAMILIES, family_of, has_long_results
 from nutpie_amd.stage_families.hmm import (MAX_HMM_STATES, _HMMOPS, _hmm_backward, _hmm_forward, _hmm_lpdf, _hmm_model, _hmm_part, _hmm_prob,  # noqa: F401
                                            _hmm_shape, _np_hmm, hmm_marginal_lpdf, hmm_state_prob)
 from nutpie_amd.stage_families.kalman import (MAX_KALMAN_STATE, _KALOPS, _kalman_args, _kalman_backward, _kalman_forward, _kalman_part,  # noqa: F401
@@ -686,8 +686,9 @@ class _Gen:
         if any(n.op == "digamma" for n in self.order):
             emit(_DIGAMMA_SOURCE)
         for fam in FAMILIES:
-            if any(n.op in fam.ops for n in self.order):
-                emit(f'#include "{fam.header}"')
+            mine = [n for n in self.order if n.op in fam.ops]
+            for header in (fam.includes(mine) or [fam.header]) if mine else []:
+                emit(f'#include "{header}"')
         emit(f"__device__ double {self.fn_name}(const NphipData& data, int dim, const double* x, double* g, double* lds, const double* shared, int lane) {{")
         # dimension lengths, data pointers (shared LDS where staged, else global), LDS scratch
         for d in m._dims.values():
@@ -1624,6 +1625,7 @@ class Model:
         try:
             self._plan_staging([logp] + grads + [e for _, e in self._det])
             gen = _Gen(self, logp, grads, waves_per_chain, profile=True)
+            self._spill(gen, waves_per_chain)      # (as compile(): what does not fit the LDS lives in the chain's block of device memory)
             src, _ = gen.source()
             compiled = self._finish(src, gen, waves_per_chain=waves_per_chain)
             x = scale * np.random.default_rng(seed).normal(size=(n_chains, self._n_dim))
@@ -1666,7 +1668,7 @@ class Model:
                 gen.spilled.append(key)
 
     def compile(self, *, init="uniform", resident: bool = True, coords=None, dims=None, waves_per_chain: int | None = None,
-                expanded_names=None, expanded_shapes=None, expand_fn=None, specialize: bool = True, var_names=None):
+                expanded_names=None, expanded_shapes=None, expand_fn=None, specialize: bool = True, var_names=None, wide_matrices: bool = False):
         """-> :class:`SymbolicModel` (a :class:`nutpie_amd.density.DensitySourceModel`).  ``waves_per_chain`` (1, 2, 4): wavefronts
         that evaluate one chain's density together — more than one pays with fewer chains than the device has SIMDs (1024), and a
         workgroup then holds ONE chain instead of four, i.e. a quarter of the per-chain LDS: the default (None) is one wave per
@@ -1675,7 +1677,11 @@ class Model:
         ``var_names`` (reference ``compile_pymc.py:821-822``, ``tests/test_pymc.py:425-468``): which of the variables that are COMPUTED from a
         draw go to the trace — the deterministics and the constrained values of transformed parameters.  ``None``: all of them; ``[]``: none;
         ``["b"]``: only ``b``.  The free variables themselves (untransformed parameters under their own name, transformed ones under their
-        unconstrained name) are always stored, as in the reference; a name that the model does not report is an error."""
+        unconstrained name) are always stored, as in the reference; a name that the model does not report is an error.
+
+        ``wide_matrices``: matrix stages (``cholesky`` / ``solve_lower``) of 33 x 33 up to 128 x 128 run on the panel routines of
+        ``csrc/wide_chain_linalg.h`` instead of being refused; a model whose matrix stages are all that wide may use 1, 2
+        or 4 waves per chain.  Narrower stages, and every model without the switch, compile as before."""
         from nutpie_amd.density import from_density_source
         import copy
 
@@ -1687,7 +1693,9 @@ class Model:
         # or a few seconds of hipcc — when one of them changes); False: one library for data of any length
         self._specialize = bool(specialize)
         self._compile_kw = dict(init=init, resident=resident, coords=coords, dims=dims, waves_per_chain=waves_per_chain, expanded_names=expanded_names,
-                                expanded_shapes=expanded_shapes, expand_fn=expand_fn, specialize=specialize, var_names=var_names)
+                                expanded_shapes=expanded_shapes, expand_fn=expand_fn, specialize=specialize, var_names=var_names,
+                                wide_matrices=wide_matrices)
+        options = {"wide_matrices": bool(wide_matrices)}      # the switches that belong to a stage family (Family.options)
         if var_names is not None:
             wanted = {getattr(v, "name", v) for v in var_names}
             unknown = wanted - {n for n, _ in self._det}
@@ -1702,7 +1710,7 @@ class Model:
         for fam in FAMILIES:      # every family's limits on its stages, and the waves per chain it runs with
             mine = [n for n in stages if n.op in fam.ops]
             if mine:
-                waves_per_chain = fam.check(mine, waves_per_chain)
+                waves_per_chain = fam.check(mine, waves_per_chain, **{k: options[k] for k in fam.options})
         self._stage_series_lengths = _series_lengths(stages)   # (the expand function's loops follow the same rule, whatever it reports)
         self._plan_staging([logp] + grads + [e for _, e in self._det])
         if waves_per_chain is None:
@@ -1833,7 +1841,7 @@ class Model:
         else:
             out_names, out_shapes = names, shapes
         egen = _Gen(self, Expr.const(0.0), [], waves_per_chain, outputs=offs, fn_name="nphip_expand") if (fixed and det) else None
-        if egen is not None and any(n.op in _STAGES and family_of(n.op).long_results for n in egen.order):
+        if egen is not None and any(n.op in _STAGES and has_long_results(n) for n in egen.order):
             # (the generated expand keeps its arrays in LDS, (4 rows per workgroup with one wave per row) + the staged data: a long scan
             #  that does not fit is expanded on the host)
             rows_per_block = 4 if waves_per_chain == 1 else 1

@@ -64,14 +64,16 @@ __all__ = ["trace", "traced_model", "UnsupportedTorchOp", "TraceResult", "linear
 class TraceResult:
     """What :func:`trace` returns: the front-end model (``.model``, a :class:`nutpie_amd.symbolic.Model`) and ``.compile()``."""
 
-    def __init__(self, model: S.Model, n_dim: int, whole: bool, n_ops: int):
-        self.model, self.n_dim, self.whole_vector, self.n_ops = model, n_dim, whole, n_ops
+    def __init__(self, model: S.Model, n_dim: int, whole: bool, n_ops: int, wide_matrices: bool = False):
+        self.model, self.n_dim, self.whole_vector, self.n_ops, self.wide_matrices = model, n_dim, whole, n_ops, wide_matrices
 
     def compile(self, **kw):
         """-> the sampler-ready model (:class:`nutpie_amd.symbolic.SymbolicModel`); reports ONE variable ``x`` of shape ``(n_dim,)``
         unless ``expand_fn`` / ``expanded_names`` / ``expanded_shapes`` say otherwise (as :func:`nutpie_amd.from_torchfunc`)."""
         kw.setdefault("expanded_names", ["x"])
         kw.setdefault("expanded_shapes", [(self.n_dim,)])
+        if self.wide_matrices:
+            kw.setdefault("wide_matrices", True)
         return self.model.compile(**kw)
 
 
@@ -1133,14 +1135,16 @@ def _run(gm, it: _Interp, x_shape, data_values: dict[str, Any]):
     raise UnsupportedTorchOp("the traced graph has no output")
 
 
-def trace(logp_fn: Callable, n_dim: int, *, batched: bool = True, shared_data: dict[str, Any] | None = None, example=None) -> TraceResult:
+def trace(logp_fn: Callable, n_dim: int, *, batched: bool = True, shared_data: dict[str, Any] | None = None, example=None,
+          wide_matrices: bool = False) -> TraceResult:
     """Trace ``logp_fn`` into a :class:`nutpie_amd.symbolic.Model`.
 
     ``logp_fn(x, **shared_data)``: with ``batched`` (the convention of :func:`nutpie_amd.from_torch_density`) ``x`` is ``[chains, n_dim]``
     and the result ``[chains]`` — traced with ONE chain, rows are independent —, otherwise ``x`` is ``[n_dim]`` and the result one
     number.  Only the forward pass is traced; the gradient is derived from the IR.  ``shared_data`` entries are passed as keyword
     arguments and keep their names as data arrays of the model; tensors the function closes over become anonymous data.
-    Python control flow on the values of ``x`` is followed for the example point only (as with every tracer)."""
+    Python control flow on the values of ``x`` is followed for the example point only (as with every tracer).  ``wide_matrices``: traced
+    matrices of up to 128 x 128 are factored and solved with (``Model.compile(wide_matrices=True)``, which ``.compile()`` then asks for)."""
     import torch
     from torch.fx.experimental.proxy_tensor import make_fx
 
@@ -1195,6 +1199,7 @@ def trace(logp_fn: Callable, n_dim: int, *, batched: bool = True, shared_data: d
     last_err = None
     for whole in (False, True):
         it = _Interp(n_dim, whole, names)
+        it.wide_matrices = bool(wide_matrices)      # (read by the rules of the family the switch belongs to)
         try:
             out, n_ops = _run(gm, it, x_shape, tens)
         except _NeedWholeVector as e:
@@ -1210,7 +1215,7 @@ def trace(logp_fn: Callable, n_dim: int, *, batched: bool = True, shared_data: d
         m = it.m
         _declare_parameters(m, it)
         m.add_logp(e)
-        return TraceResult(m, n_dim, whole, n_ops)
+        return TraceResult(m, n_dim, whole, n_ops, bool(wide_matrices))
     raise UnsupportedTorchOp(f"could not map the position vector: {last_err}")
 
 
@@ -1266,7 +1271,7 @@ def _traced_model_class():
 
 def traced_model(ndim: int, density_fn: Callable, *, batched: bool = True, shared_data: dict[str, Any] | None = None, expand_fn: Callable | None = None,
                  expanded_shapes=None, expanded_names=None, coords=None, dims=None, init="uniform", reparameterized_names=None,
-                 waves_per_chain: int | None = None, resident: bool = True):
+                 waves_per_chain: int | None = None, resident: bool = True, wide_matrices: bool = False):
     """``density_fn`` traced and compiled: what :func:`nutpie_amd.from_torch_density` returns on its compiled path.  ``expand_fn``
     (numpy ``[N, ndim]`` -> dict of arrays, with ``expanded_names`` / ``expanded_shapes``) as in :func:`nutpie_amd.from_torchfunc`."""
     import dataclasses
@@ -1275,7 +1280,7 @@ def traced_model(ndim: int, density_fn: Callable, *, batched: bool = True, share
         raise ValueError("expand_fn needs expanded_names and expanded_shapes")
 
     def build(shared):
-        tr = trace(density_fn, ndim, batched=batched, shared_data=shared)
+        tr = trace(density_fn, ndim, batched=batched, shared_data=shared, wide_matrices=wide_matrices)
         user_expand = None
         if expand_fn is not None:
             def user_expand(positions, /, **_model_data):      # (the model's data arrays are the trace's, not the user's keywords)
