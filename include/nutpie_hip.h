@@ -321,9 +321,9 @@ int nphip_batched_eigh(uint64_t n_batch, uint64_t order, double* a_device, doubl
  *   lambda[n][k_max]    eigenvalues (1 beyond k_used)
  * of  M^-1 = D^1/2 (I + V (Lambda - I) V') D^1/2:  the geometric mean of the draw covariance and the inverse gradient covariance
  * (regularised by gamma) projected onto the span of the n_pick basis draws pick[0 .. n_pick) (indices into the window, host memory) and their
- * gradients, eigenvalues outside [1 / cutoff, cutoff] kept, at most k_max <= 16.  One workgroup per chain, LDS-resident, the four symmetric
- * eigenproblems of order 2 n_pick <= 64 by a one-sided Jacobi method (nutpie_amd/csrc/lowrank_est.hip).  scratch: n * 4112 doubles of
- * device memory.  max_workgroups (0 = one per chain): the launch's size — a workgroup wants a CU's LDS to itself, so beside a
+ * gradients, eigenvalues outside [1 / cutoff, cutoff] kept, at most k_max <= 16.  One workgroup per chain, LDS-resident, the two symmetric
+ * eigenproblems of order 2 n_pick <= 64 by a one-sided Jacobi method (nutpie_amd/csrc/lowrank_est.hip; what it shares with the wide
+ * kernel below: nutpie_amd/csrc/lowrank_est_common.h).  scratch: n * 4112 doubles of device memory.  max_workgroups (0 = one per chain): the launch's size — a workgroup wants a CU's LDS to itself, so beside a
  * running engine kernel the caller caps it at the CUs that kernel leaves idle (a workgroup then takes several chains in turn).
  * Asynchronous on `stream`.  nphip_low_rank_estimate_supported: whether a shape is inside what the kernel covers
  * (dim <= 512, n_pick <= 32 and <= dim, k_max <= 16). */

@@ -91,7 +91,7 @@ _lib_lock = threading.Lock()
 
 def build(force: bool = False) -> str:
     """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("kernels.hip", "host.hip", "linalg.hip", "lowrank_est.hip", "lowrank_est_wide.hip", "engine_types.h", "kernel_families.h", "drive_plan.h", "dense_tile.h", "Makefile")]
+    srcs = [os.path.join(_CSRC, f) for f in ("kernels.hip", "host.hip", "linalg.hip", "lowrank_est.hip", "lowrank_est_wide.hip", "lowrank_est_common.h", "engine_types.h", "kernel_families.h", "drive_plan.h", "dense_tile.h", "Makefile")]
     srcs += [os.path.join(_HERE, "..", "include", f) for f in ("nutpie_hip.h", "nphip_spec.h")]
     stale = not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -171,12 +171,10 @@ def lib():
             L.nphip_sampler_set_evals_per_launch.argtypes = [C.c_void_p, C.c_int32]
             L.nphip_sampler_release.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
             L.nphip_batched_eigh.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.nphip_low_rank_estimate_supported.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
-            L.nphip_low_rank_estimate.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
-                                                  C.c_double, C.c_double, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-            L.nphip_low_rank_estimate_wide_supported.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
-            L.nphip_low_rank_estimate_wide.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
-                                                       C.c_double, C.c_double, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+            for estimator in (L.nphip_low_rank_estimate, L.nphip_low_rank_estimate_wide):   # (one signature: include/nutpie_hip.h)
+                estimator.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                      C.c_double, C.c_double, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+            L.nphip_low_rank_estimate_supported.argtypes = L.nphip_low_rank_estimate_wide_supported.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
             L.nphip_test_eigh_stage.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
             L.nphip_launch_defaults.argtypes = [C.POINTER(_Launch)]
             L.nphip_default_evals_per_launch.argtypes = [C.c_uint64]
@@ -988,6 +986,65 @@ def batched_eigh(A, _stage=0):
     return w, V
 
 
+WIDE_WORKGROUP_SCRATCH = 54272   # doubles per workgroup (include/nutpie_hip.h; lowrank_est_wide.hip asserts the figure)
+WIDE_DIAG_WORDS = 16             # per chain, behind the workgroups' blocks
+_wide_scratch = {}               # (device, stream) -> the scratch of the largest launch so far (grow-only: launches on one stream are ordered)
+
+# What differs between the two estimator kernels above the C-ABI, by the name of the public function.  scratch(n, grid): shape of the
+# scratch a launch needs; kept: where a scratch stays for the next launch on its device and stream, or None for a fresh one per call;
+# diag(scratch, n, grid): the chains' 16 diagnostic words, a view [n, 16].
+_LR_KERNELS = {
+    "low_rank_estimate": dict(
+        entry="nphip_low_rank_estimate", scratch=lambda n, grid: (max(n, 1), 4112), kept=None, diag=lambda scratch, n, grid: scratch[:n, 4096:],
+        refusal="nphip_low_rank_estimate refused the shape (dim <= 512, at most 32 basis draws, k_max <= 16, cutoff > 1, gamma > 0)"),
+    "low_rank_estimate_wide": dict(
+        entry="nphip_low_rank_estimate_wide", scratch=lambda n, grid: (max(grid, 1) * WIDE_WORKGROUP_SCRATCH + max(n, 1) * WIDE_DIAG_WORDS,), kept=_wide_scratch,
+        diag=lambda scratch, n, grid: scratch[grid * WIDE_WORKGROUP_SCRATCH: grid * WIDE_WORKGROUP_SCRATCH + n * WIDE_DIAG_WORDS].view(n, WIDE_DIAG_WORDS),
+        refusal="nphip_low_rank_estimate_wide refused the shape (dim <= 1024, at most 64 basis draws and no more than draws or dimensions, "
+                "1 <= k_max <= 16, cutoff > 1, gamma > 0, pick inside the window)"),
+}
+
+
+def _lr_launch(fn, draws, grads, chains, lo, hi, pick, gamma, cutoff, k_max, max_workgroups):
+    """One launch for the public function ``fn``, by its row of ``_LR_KERNELS``; leaves ``fn.last_scratch`` and ``fn.last_diag``."""
+    import torch
+
+    name, K = fn.__name__, _LR_KERNELS[fn.__name__]
+    if not (draws.is_cuda and grads.is_cuda and draws.dtype == torch.float64 and grads.dtype == torch.float64 and draws.dim() == 3 and draws.shape == grads.shape):
+        raise ValueError(name + ": CUDA float64 tensors [chains, draws, dim] of one shape")
+    if draws.stride(2) != 1 or grads.stride(2) != 1 or draws.stride() != grads.stride():
+        raise ValueError(name + ": rows must be contiguous and both arrays laid out alike")
+    D, m = int(draws.shape[2]), int(hi) - int(lo)
+    pick = np.ascontiguousarray(pick, dtype=np.int32)
+    n = int(draws.shape[0]) if chains is None else int(chains.numel())
+    if chains is not None and not (chains.is_cuda and chains.dtype == torch.int64 and chains.is_contiguous()):
+        raise ValueError(name + ": chains must be a contiguous CUDA int64 tensor")
+    dev = draws.device
+    sig2 = torch.empty(n, D, dtype=torch.float64, device=dev)
+    V = torch.empty(n, int(k_max), D, dtype=torch.float64, device=dev)
+    lam = torch.empty(n, int(k_max), dtype=torch.float64, device=dev)
+    k_used = torch.empty(n, dtype=torch.int32, device=dev)
+    grid = int(max_workgroups) if 0 < int(max_workgroups) < n else n
+    shape, kept = K["scratch"](n, grid), K["kept"]
+    off = int(lo) * int(draws.stride(1)) * 8
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        scratch = None if kept is None else kept.get((dev, stream))
+        if scratch is None or scratch.numel() < shape[0]:
+            scratch = torch.empty(*shape, dtype=torch.float64, device=dev)
+            if kept is not None:
+                kept[(dev, stream)] = scratch
+        rc = getattr(lib(), K["entry"])(C.c_uint64(n), C.c_uint64(D), C.c_uint64(m), C.c_uint64(len(pick)), pick.ctypes.data_as(C.c_void_p),
+                                        C.c_void_p(draws.data_ptr() + off), C.c_void_p(grads.data_ptr() + off), C.c_int64(int(draws.stride(0))),
+                                        C.c_int64(int(draws.stride(1))), None if chains is None else C.c_void_p(chains.data_ptr()), C.c_double(float(gamma)),
+                                        C.c_double(float(cutoff)), C.c_uint64(int(k_max)), C.c_void_p(sig2.data_ptr()), C.c_void_p(V.data_ptr()),
+                                        C.c_void_p(lam.data_ptr()), C.c_void_p(k_used.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_uint64(int(max_workgroups)), C.c_void_p(stream))
+    if rc != NPHIP_OK:
+        raise RuntimeError(K["refusal"])
+    fn.last_scratch, fn.last_diag = scratch, K["diag"](scratch, n, grid)
+    return sig2, V, lam, k_used
+
+
 def low_rank_estimate_supported(dim: int, m: int, n_pick: int, k_max: int) -> bool:
     return bool(lib().nphip_low_rank_estimate_supported(C.c_uint64(int(dim)), C.c_uint64(int(m)), C.c_uint64(int(n_pick)), C.c_uint64(int(k_max))))
 
@@ -996,45 +1053,14 @@ def low_rank_estimate(draws, grads, chains, lo, hi, pick, gamma, cutoff, k_max=1
     """``nphip_low_rank_estimate`` (nutpie_amd/csrc/lowrank_est.hip): the low-rank metric of ``chains`` (a CUDA int64 tensor of rows of
     ``draws``, or None for all rows) from the window ``draws[:, lo:hi]``, ``grads[:, lo:hi]`` — CUDA float64 tensors ``[n_all, T, D]``
     with contiguous rows, e.g. views of the engine's trace — and the basis draws ``pick`` (indices into the window).  Returns
-    ``(sigma2[n, D], V[n, k_max, D], lam[n, k_max], k_used[n] int32)`` on torch's current stream, nothing synchronised."""
-    import torch
-
-    if not (draws.is_cuda and grads.is_cuda and draws.dtype == torch.float64 and grads.dtype == torch.float64 and draws.dim() == 3 and draws.shape == grads.shape):
-        raise ValueError("low_rank_estimate: CUDA float64 tensors [chains, draws, dim] of one shape")
-    if draws.stride(2) != 1 or grads.stride(2) != 1 or draws.stride() != grads.stride():
-        raise ValueError("low_rank_estimate: rows must be contiguous and both arrays laid out alike")
-    D, m = int(draws.shape[2]), int(hi) - int(lo)
-    pick = np.ascontiguousarray(pick, dtype=np.int32)
-    n = int(draws.shape[0]) if chains is None else int(chains.numel())
-    if chains is not None and not (chains.is_cuda and chains.dtype == torch.int64 and chains.is_contiguous()):
-        raise ValueError("low_rank_estimate: chains must be a contiguous CUDA int64 tensor")
-    dev = draws.device
-    sig2 = torch.empty(n, D, dtype=torch.float64, device=dev)
-    V = torch.empty(n, int(k_max), D, dtype=torch.float64, device=dev)
-    lam = torch.empty(n, int(k_max), dtype=torch.float64, device=dev)
-    k_used = torch.empty(n, dtype=torch.int32, device=dev)
-    scratch = torch.empty(max(n, 1), 4112, dtype=torch.float64, device=dev)
-    off = int(lo) * int(draws.stride(1)) * 8
-    with torch.cuda.device(dev):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = lib().nphip_low_rank_estimate(C.c_uint64(n), C.c_uint64(D), C.c_uint64(m), C.c_uint64(len(pick)), pick.ctypes.data_as(C.c_void_p),
-                                           C.c_void_p(draws.data_ptr() + off), C.c_void_p(grads.data_ptr() + off), C.c_int64(int(draws.stride(0))),
-                                           C.c_int64(int(draws.stride(1))), None if chains is None else C.c_void_p(chains.data_ptr()), C.c_double(float(gamma)),
-                                           C.c_double(float(cutoff)), C.c_uint64(int(k_max)), C.c_void_p(sig2.data_ptr()), C.c_void_p(V.data_ptr()),
-                                           C.c_void_p(lam.data_ptr()), C.c_void_p(k_used.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_uint64(int(max_workgroups)), st)
-    if rc != NPHIP_OK:
-        raise RuntimeError("nphip_low_rank_estimate refused the shape (dim <= 512, at most 32 basis draws, k_max <= 16, cutoff > 1, gamma > 0)")
-    low_rank_estimate.last_scratch = scratch   # (diagnostics: words 4096.. of every chain's row — scratch/r6_lr_native.py)
-    return sig2, V, lam, k_used
+    ``(sigma2[n, D], V[n, k_max, D], lam[n, k_max], k_used[n] int32)`` on torch's current stream, nothing synchronised.
+    ``low_rank_estimate.last_scratch`` is the launch's scratch ``[n, 4112]`` and ``.last_diag`` its words 4096.. ``[n, 16]``: the diagnostics
+    (two unused, sweeps of the two Jacobi solvers, cycles — scratch/r6_lr_native.py)."""
+    return _lr_launch(low_rank_estimate, draws, grads, chains, lo, hi, pick, gamma, cutoff, k_max, max_workgroups)
 
 
 def low_rank_estimate_wide_supported(dim: int, m: int, n_pick: int, k_max: int) -> bool:
     return bool(lib().nphip_low_rank_estimate_wide_supported(C.c_uint64(int(dim)), C.c_uint64(int(m)), C.c_uint64(int(n_pick)), C.c_uint64(int(k_max))))
-
-
-WIDE_WORKGROUP_SCRATCH = 54272   # doubles per workgroup (include/nutpie_hip.h; lowrank_est_wide.hip asserts the figure)
-WIDE_DIAG_WORDS = 16             # per chain, behind the workgroups' blocks
-_wide_scratch = {}               # (device, stream) -> the scratch of the largest launch so far (grow-only: launches on one stream are ordered)
 
 
 def low_rank_estimate_wide(draws, grads, chains, lo, hi, pick, gamma, cutoff, k_max=16, max_workgroups=0):
@@ -1042,41 +1068,14 @@ def low_rank_estimate_wide(draws, grads, chains, lo, hi, pick, gamma, cutoff, k_
     64 basis draws — same arguments, same outputs, same semantics.  The scratch is kept per device and stream and only grows (launches
     on one stream are ordered); ``low_rank_estimate_wide.last_diag`` is a view ``[n, 16]`` of the last launch's diagnostic words (sweeps
     of the two Jacobi passes, rank, cycles), valid until the next launch on that stream."""
-    import torch
+    return _lr_launch(low_rank_estimate_wide, draws, grads, chains, lo, hi, pick, gamma, cutoff, k_max, max_workgroups)
 
-    if not (draws.is_cuda and grads.is_cuda and draws.dtype == torch.float64 and grads.dtype == torch.float64 and draws.dim() == 3 and draws.shape == grads.shape):
-        raise ValueError("low_rank_estimate_wide: CUDA float64 tensors [chains, draws, dim] of one shape")
-    if draws.stride(2) != 1 or grads.stride(2) != 1 or draws.stride() != grads.stride():
-        raise ValueError("low_rank_estimate_wide: rows must be contiguous and both arrays laid out alike")
-    D, m = int(draws.shape[2]), int(hi) - int(lo)
-    pick = np.ascontiguousarray(pick, dtype=np.int32)
-    n = int(draws.shape[0]) if chains is None else int(chains.numel())
-    if chains is not None and not (chains.is_cuda and chains.dtype == torch.int64 and chains.is_contiguous()):
-        raise ValueError("low_rank_estimate_wide: chains must be a contiguous CUDA int64 tensor")
-    dev = draws.device
-    sig2 = torch.empty(n, D, dtype=torch.float64, device=dev)
-    V = torch.empty(n, int(k_max), D, dtype=torch.float64, device=dev)
-    lam = torch.empty(n, int(k_max), dtype=torch.float64, device=dev)
-    k_used = torch.empty(n, dtype=torch.int32, device=dev)
-    grid = int(max_workgroups) if 0 < int(max_workgroups) < n else n
-    words = max(grid, 1) * WIDE_WORKGROUP_SCRATCH + max(n, 1) * WIDE_DIAG_WORDS
-    off = int(lo) * int(draws.stride(1)) * 8
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        scratch = _wide_scratch.get((dev, stream))
-        if scratch is None or scratch.numel() < words:
-            scratch = _wide_scratch[(dev, stream)] = torch.empty(words, dtype=torch.float64, device=dev)
-        st = C.c_void_p(stream)
-        rc = lib().nphip_low_rank_estimate_wide(C.c_uint64(n), C.c_uint64(D), C.c_uint64(m), C.c_uint64(len(pick)), pick.ctypes.data_as(C.c_void_p),
-                                                C.c_void_p(draws.data_ptr() + off), C.c_void_p(grads.data_ptr() + off), C.c_int64(int(draws.stride(0))),
-                                                C.c_int64(int(draws.stride(1))), None if chains is None else C.c_void_p(chains.data_ptr()), C.c_double(float(gamma)),
-                                                C.c_double(float(cutoff)), C.c_uint64(int(k_max)), C.c_void_p(sig2.data_ptr()), C.c_void_p(V.data_ptr()),
-                                                C.c_void_p(lam.data_ptr()), C.c_void_p(k_used.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_uint64(int(max_workgroups)), st)
-    if rc != NPHIP_OK:
-        raise RuntimeError("nphip_low_rank_estimate_wide refused the shape (dim <= 1024, at most 64 basis draws and no more than draws or dimensions, "
-                           "1 <= k_max <= 16, cutoff > 1, gamma > 0, pick inside the window)")
-    low_rank_estimate_wide.last_diag = scratch[grid * WIDE_WORKGROUP_SCRATCH: grid * WIDE_WORKGROUP_SCRATCH + n * WIDE_DIAG_WORDS].view(n, WIDE_DIAG_WORDS)
-    return sig2, V, lam, k_used
+
+def low_rank_estimator_for(dim: int, m: int, n_pick: int, k_max: int):
+    """The estimator that takes the shape: :func:`low_rank_estimate` where it does, else :func:`low_rank_estimate_wide`, else None."""
+    if low_rank_estimate_supported(dim, m, n_pick, k_max):
+        return low_rank_estimate
+    return low_rank_estimate_wide if low_rank_estimate_wide_supported(dim, m, n_pick, k_max) else None
 
 
 def default_evals_per_launch(dim: int) -> int:

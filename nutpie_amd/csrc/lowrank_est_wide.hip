@@ -1,9 +1,7 @@
 // nutpie-hip: the window estimator of adaptation="low_rank" as one kernel, WIDE shape (include/nutpie_hip.h: nphip_low_rank_estimate_wide):
 // up to 1024 dimensions and 64 basis draws, i.e. a subspace problem of order R = 128 — what low_rank.basis_draws_for asks for above 256
-// dimensions, which lowrank_est.hip (R = 64, four R x R matrices in LDS) does not cover.  Same contract, same semantics (moments over all m
-// draws, a constant coordinate is its own mean, a non-finite window or an overflowed Gram matrix is exactly the identity, rank at 1e-10 of
-// the first Cholesky pivot, spectrum clamped to the trace bounds, re-centred on the lower median over the live directions, the k_max
-// directions by |log| outside the cutoff with ties to the lower index); lowrank_est.hip's header comment has the estimator itself.
+// dimensions, which lowrank_est.hip (R = 64, four R x R matrices in LDS) does not cover.  lowrank_est.hip's header comment has the
+// estimator itself; lowrank_est_common.h has the contract both kernels keep and the code they share.
 //
 // What is different: ONE R x R matrix lives in LDS at a time (column stride 130: 133 120 B of the CU's 163 840), everything else is parked
 // in a per-workgroup block of device memory (L2-resident), and neither eigenproblem is formed as a symmetric matrix.  With Cg = Rc Rc' and
@@ -19,47 +17,27 @@
 //   registers -> LDS;  H Jacobi;  I scaling and back substitution with Rc read from scratch;  J Jacobi;  L selection (128 threads);
 //   M T = L^-T W_sel with L read from scratch;  N V = Z_perm' T.
 // A chain's result is a fixed function of its window and the settings: no atomics, nothing depends on the grid or on which workgroup ran it.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "../../include/nutpie_hip.h"
+#include "lowrank_est_common.h"
 
 namespace nphip_lrest_wide {
 
-constexpr int R = 128;         // order of the subspace problem (2 x basis draws, zero-padded)
-constexpr int LD = 130;        // column stride of the matrix in LDS (even: 16-byte accesses; 130 = 2 mod 32 spreads a row over the banks)
-constexpr int kThreads = 1024; // four waves per SIMD
+using namespace nphip_lrest_common;
+
+struct Shape {
+    static constexpr int R = 128;          // order of the subspace problem (2 x basis draws, zero-padded)
+    static constexpr int LD = 130;         // column stride of the matrix in LDS (even: 16-byte accesses; 130 = 2 mod 32 spreads a row over the banks)
+    static constexpr int kThreads = 1024;  // four waves per SIMD
+    static constexpr int kMaxDim = 1024;
+    static constexpr int kMaxPick = 64;
+};
+constexpr int R = Shape::R, LD = Shape::LD, kThreads = Shape::kThreads, kMaxDim = Shape::kMaxDim, kMaxPick = Shape::kMaxPick;
 constexpr int kWaves = kThreads / 64;
-constexpr int LP = 16;         // lanes per column pair of a Jacobi step: one DPP row
-constexpr int NJ = (R / LP) / 2;   // 16-byte pieces of a column per lane
-constexpr int kMaxSweeps = 30;
-constexpr double kJacobiTol2 = 1e-28;   // a pair of columns is orthogonal when |g_p . g_q| <= 1e-14 |g_p| |g_q|
-constexpr int kMaxDim = 1024;
-constexpr int kMaxPick = 64;
-constexpr int kMaxK = 16;
 constexpr int kDiag = 16;      // diagnostic words per chain
 // per workgroup, in doubles: mean_x, mean_g, stds [kMaxDim each]; L, Cx, Cg -> Rc [R x R each]; the selected columns [R x kMaxK]
 constexpr int kWgScratch = 3 * kMaxDim + 3 * R * R + R * kMaxK;
 static_assert(kWgScratch == 54272, "include/nutpie_hip.h and nutpie_amd/_lib.py state this figure");
+typedef nphip_lrest_common::Params<kMaxPick> Params;   // scratch: [grid][kWgScratch], then [n][kDiag]
 
-struct Params {
-    const double* draws;
-    const double* grads;
-    long long chain_stride, draw_stride;
-    const long long* chains;   // device, or null: chain = slot
-    int n, dim, m, b;
-    int pick[kMaxPick];
-    double gamma, log_cutoff;
-    int k_max;
-    double* sig2;     // [n][dim]
-    double* V;        // [n][k_max][dim]
-    double* lam;      // [n][k_max]
-    int* k_used;      // [n]
-    double* scratch;  // [grid][kWgScratch], then [n][kDiag]
-};
-
-#define M_(A, r, c) (A)[(c) * LD + (r)]
 // The thread index, made opaque to the compiler at the start of every phase: addresses derived from it are then computed where a phase
 // uses them, not once ahead of the loop over chains — hoisted there they outlive every phase and the kernel spills (190 registers without this).
 #define NPHIP_FRESH_TID() do { asm volatile("" : "+v"(tid)); ri = tid & 31; cj = tid >> 5; } while (0)
@@ -76,34 +54,6 @@ __device__ __forceinline__ double block_sum(double v, double* red, int tid) {
     return t;
 }
 
-// 1 / sqrt(x) and 1 / x to full precision from the hardware's seeds (lowrank_est.hip has the reasoning)
-__device__ __forceinline__ double fast_rsq(double x) {
-    double y = __builtin_amdgcn_rsq(x);
-    const double hx = 0.5 * x;
-    y = fma(y, fma(-hx * y, y, 0.5), y);
-    y = fma(y, fma(-hx * y, y, 0.5), y);
-    return y;
-}
-__device__ __forceinline__ double fast_rcp(double x) {
-    double y = __builtin_amdgcn_rcp(x);
-    y = fma(y, fma(-x, y, 1.0), y);
-    y = fma(y, fma(-x, y, 1.0), y);
-    return y;
-}
-
-// sum over the 16 lanes (one DPP row) that share a column pair, returned to all of them
-template <int CTRL> __device__ __forceinline__ double dpp_get(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ void pair_sum3(double& a, double& b, double& g) {
-    a += dpp_get<0xB1>(a); b += dpp_get<0xB1>(b); g += dpp_get<0xB1>(g);
-    a += dpp_get<0x4E>(a); b += dpp_get<0x4E>(b); g += dpp_get<0x4E>(g);
-    a += dpp_get<0x141>(a); b += dpp_get<0x141>(b); g += dpp_get<0x141>(g);
-    a += dpp_get<0x140>(a); b += dpp_get<0x140>(b); g += dpp_get<0x140>(g);
-}
-
 // One-sided Jacobi (Hestenes) on the columns of F (R x R in LDS): on return the columns are mutually orthogonal, F_out = F_in J with J
 // orthogonal — F F' is unchanged, column j is (eigenvector j of F F') x (eigenvalue j)^1/2.  J is not accumulated.  64 disjoint column
 // pairs per step by the round-robin tournament (127 steps a sweep), 16 lanes per pair, 8 elements of each column per lane, one barrier
@@ -113,43 +63,25 @@ __device__ int jacobi(double* __restrict__ F, double* __restrict__ red, int tid,
     for (int idx = tid; idx < R * R; idx += kThreads) { const double a = M_(F, idx & (R - 1), idx >> 7); fro = fma(a, a, fro); }
     fro = block_sum(fro, red, tid);
     const double tiny2 = fro * rel_tiny + 1e-300;
-    const int pr = tid / LP, sub = tid % LP;
+    const int pr = tid / kPairLanes, sub = tid % kPairLanes;
     int sweeps = 0;
     for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
         int rotated = 0;
         ++sweeps;
         for (int step = 0; step < R - 1; ++step) {
             int p, q;
-            if (pr == 0) { p = R - 1; q = step; }
-            else { p = step + pr; p -= (p >= R - 1) ? R - 1 : 0; q = step + (R - 1) - pr; q -= (q >= R - 1) ? R - 1 : 0; }
+            jacobi_pair<Shape>(pr, step, p, q);
             double* gp = F + p * LD + 2 * sub;
             double* gq = F + q * LD + 2 * sub;
-            double2 xp[NJ], xq[NJ];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) { xp[j] = *(const double2*)(gp + 2 * LP * j); xq[j] = *(const double2*)(gq + 2 * LP * j); }
-            double a = 0.0, b = 0.0, g = 0.0;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                a = fma(xp[j].x, xp[j].x, a); a = fma(xp[j].y, xp[j].y, a);
-                b = fma(xq[j].x, xq[j].x, b); b = fma(xq[j].y, xq[j].y, b);
-                g = fma(xp[j].x, xq[j].x, g); g = fma(xp[j].y, xq[j].y, g);
-            }
-            pair_sum3(a, b, g);
-            if (a > tiny2 && b > tiny2 && g * g > kJacobiTol2 * (a * b)) {   // |g| > tol sqrt(a b)
-                // tan of the rotation angle: t = sign(d) 2g / (|d| + sqrt(d^2 + 4 g^2)), d = b - a;  c = 1 / sqrt(1 + t^2), s = c t
-                const double d = b - a, g2 = 2.0 * g;
-                const double h2 = fma(d, d, g2 * g2);
-                const double h = h2 * fast_rsq(h2);
-                const double t = copysign(g2, d * g2) * fast_rcp(fabs(d) + h);
-                const double c = fast_rsq(fma(t, t, 1.0)), s = c * t;
+            JacobiStep<Shape>::Col xp, xq;
+            jacobi_load<Shape>(gp, gq, xp, xq);
+            double a, b, g;
+            jacobi_dots<Shape>(xp, xq, a, b, g);
+            if (a > tiny2 && b > tiny2 && g * g > kJacobiTol2 * (a * b)) {   // |g| > tol sqrt(a b); columns below tiny2 are zero
+                double c, s;
+                jacobi_rotation(a, b, g, c, s);
                 rotated = 1;
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    double2 u, v;
-                    u.x = fma(c, xp[j].x, -(s * xq[j].x)); u.y = fma(c, xp[j].y, -(s * xq[j].y));
-                    v.x = fma(s, xp[j].x, c * xq[j].x);    v.y = fma(s, xp[j].y, c * xq[j].y);
-                    *(double2*)(gp + 2 * LP * j) = u; *(double2*)(gq + 2 * LP * j) = v;
-                }
+                jacobi_rotate_store<Shape>(gp, gq, xp, xq, c, s);
             }
             __syncthreads();
         }
@@ -326,11 +258,13 @@ __device__ void estimate_one(const Params& P, const int slot, double* lds) {
     const long long chain = P.chains ? P.chains[slot] : (long long)slot;
     const double* X = P.draws + chain * P.chain_stride;
     const double* Gx = P.grads + chain * P.chain_stride;
-    const int D = P.dim, m = P.m, b = P.b, r = 2 * b;
+    const int D = P.dim, m = P.m, b = P.b;
     const double inf = __builtin_inf();
     const long long tk0_ = (long long)__builtin_readcyclecounter();
 
-    // ---- A. moments over the whole window (two passes) and the diagonal scaling sqrt(std(x) / std(g)); a thread has its own dimensions
+    // ---- A. moments over the whole window (two passes) and the diagonal scaling sqrt(std(x) / std(g)); a thread has its own dimensions.
+    //         lowrank_est_common.h: window_moments, written out — and so is phase N below (write_columns): called through the header, by
+    //         value or through P, this kernel spills more registers at its ceiling of 128.  A change to either phase is made in both places.
     int bad = 0;
     for (int i = tid; i < D; i += kThreads) {
         double sx = 0.0, sg = 0.0;
@@ -366,12 +300,7 @@ __device__ void estimate_one(const Params& P, const int slot, double* lds) {
     }
     __syncthreads();   // (also makes the scratch writes visible to the workgroup)
 
-    // Z(t, i): row t of the scaled basis — draws for t < b, gradients for b <= t < 2b, zero padding beyond
-    auto zval = [&](int t, int i) -> double {
-        if (bad || t >= r) return 0.0;
-        if (t < b) return (X[(long long)pick[t] * P.draw_stride + i] - mean_x[i]) / stds[i];
-        return (Gx[(long long)pick[t - b] * P.draw_stride + i] - mean_g[i]) * stds[i];
-    };
+    const BasisRows zval{X, Gx, pick, P.draw_stride, mean_x, mean_g, stds, b, bad};
 
     // a thread's 4 x 4 block of an R x R product: rows ri + 32 i', columns cj + 32 j' (interleaved: the reads along a row of the matrix
     // then fall on 16 bank pairs, and cj is uniform over half a wave): ri = tid & 31, cj = tid >> 5
@@ -459,10 +388,7 @@ __device__ void estimate_one(const Params& P, const int slot, double* lds) {
     trx = block_sum(trx, red, tid);
     trg = block_sum(trg, red, tid);
     if (bad || nonfin) {
-        for (int i = tid; i < D; i += kThreads) P.sig2[(size_t)slot * D + i] = 1.0;
-        for (int idx = tid; idx < P.k_max * D; idx += kThreads) P.V[(size_t)slot * P.k_max * D + idx] = 0.0;
-        if (tid < P.k_max) P.lam[(size_t)slot * P.k_max + tid] = 1.0;
-        if (tid == 0) P.k_used[slot] = 0;
+        write_identity<Shape>(P, slot, tid);
         if (tid < kDiag) dg[tid] = 0.0;
         return;
     }
@@ -531,9 +457,7 @@ __device__ void estimate_one(const Params& P, const int slot, double* lds) {
     // ---- L. spectrum: clamped, re-centred, the k_max directions chosen (select)
     const double centre = select(es, le, lv, red, isel, trx, trg, P.gamma, P.log_cutoff, P.k_max, tid);
     const int n_used = isel[kMaxK];
-    for (int i = tid; i < D; i += kThreads) { const double s = stds[i] * sqrt(centre); P.sig2[(size_t)slot * D + i] = s * s; }
-    if (tid < P.k_max) P.lam[(size_t)slot * P.k_max + tid] = (tid < n_used) ? es[isel[tid]] : 1.0;
-    if (tid == 0) P.k_used[slot] = n_used;
+    write_spectrum<Shape>(P, slot, stds, centre, es, isel, n_used, tid);
 
     NPHIP_FRESH_TID();
     // ---- M. T = L^-T W[:, sel]  (rank x n_used; rows beyond the rank are zero): the selected columns, normalised, go through the scratch
@@ -555,6 +479,7 @@ __device__ void estimate_one(const Params& P, const int slot, double* lds) {
     NPHIP_FRESH_TID();
     solve_lt(gL, A, rank, kMaxK, tid);
     NPHIP_FRESH_TID();
+    // (N: lowrank_est_common.h: write_columns, kept here — see phase A)
     for (int i = tid; i < D; i += kThreads) {
         double acc[kMaxK];
 #pragma unroll
@@ -600,27 +525,13 @@ constexpr size_t kLdsBytes = ((size_t)R * LD + 3 * R + 24) * sizeof(double) + (k
 }  // namespace nphip_lrest_wide
 
 extern "C" int nphip_low_rank_estimate_wide_supported(uint64_t dim, uint64_t m, uint64_t n_pick, uint64_t k_max) {
-    using namespace nphip_lrest_wide;
-    return (dim >= 1 && dim <= (uint64_t)kMaxDim && m >= 2 && n_pick >= 1 && n_pick <= (uint64_t)kMaxPick && n_pick <= m && n_pick <= dim &&
-            k_max >= 1 && k_max <= (uint64_t)kMaxK) ? 1 : 0;
+    return nphip_lrest_common::shape_supported<nphip_lrest_wide::Shape>(dim, m, n_pick, k_max) ? 1 : 0;
 }
 
 extern "C" int nphip_low_rank_estimate_wide(uint64_t n, uint64_t dim, uint64_t m, uint64_t n_pick, const int32_t* pick, const double* draws, const double* grads,
                                             int64_t chain_stride, int64_t draw_stride, const int64_t* chains_device, double gamma, double cutoff, uint64_t k_max,
                                             double* sigma2, double* V, double* lambda, int32_t* k_used, double* scratch, uint64_t max_workgroups, void* stream) {
     using namespace nphip_lrest_wide;
-    if (n == 0) return NPHIP_OK;
-    if (!nphip_low_rank_estimate_wide_supported(dim, m, n_pick, k_max) || !pick || !draws || !grads || !sigma2 || !V || !lambda || !k_used || !scratch || !(cutoff > 1.0) || !(gamma > 0.0))
-        return NPHIP_ERR;
-    Params P;
-    P.draws = draws; P.grads = grads; P.chain_stride = chain_stride; P.draw_stride = draw_stride; P.chains = (const long long*)chains_device;
-    P.n = (int)n; P.dim = (int)dim; P.m = (int)m; P.b = (int)n_pick;
-    for (int i = 0; i < kMaxPick; ++i) P.pick[i] = i < (int)n_pick ? pick[i] : 0;
-    for (int i = 0; i < (int)n_pick; ++i) if (pick[i] < 0 || (uint64_t)pick[i] >= m) return NPHIP_ERR;
-    P.gamma = gamma; P.log_cutoff = log(cutoff); P.k_max = (int)k_max;
-    P.sig2 = sigma2; P.V = V; P.lam = lambda; P.k_used = k_used; P.scratch = scratch;
-    if (hipFuncSetAttribute((const void*)k_lr_estimate_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes) != hipSuccess) return NPHIP_ERR;
-    const uint64_t grid = (max_workgroups > 0 && max_workgroups < n) ? max_workgroups : n;
-    hipLaunchKernelGGL(k_lr_estimate_wide, dim3((unsigned)grid), dim3(kThreads), kLdsBytes, (hipStream_t)stream, P);
-    return hipGetLastError() == hipSuccess ? NPHIP_OK : NPHIP_ERR;
+    return nphip_lrest_common::launch<Shape>(k_lr_estimate_wide, kLdsBytes, n, dim, m, n_pick, pick, draws, grads, chain_stride, draw_stride, chains_device, gamma, cutoff,
+                                             k_max, sigma2, V, lambda, k_used, scratch, max_workgroups, stream);
 }

@@ -334,13 +334,10 @@ def estimate_window(draws, grads, chains, lo: int, hi: int, gamma: float, cutoff
     if NATIVE_ESTIMATOR and draws.is_cuda and k_max <= 16 and len(pick) <= D:
         from nutpie_amd import _lib
 
-        if _lib.low_rank_estimate_supported(D, m, len(pick), k_max):
+        kernel = _lib.low_rank_estimator_for(D, m, len(pick), k_max)
+        if kernel is not None:
             idx = None if chains is None else torch.as_tensor(np.asarray(chains, dtype=np.int64), device=draws.device)
-            sig2, V, lam, _ = _lib.low_rank_estimate(draws, grads, idx, lo, hi, pick, gamma, cutoff, k_max, max_workgroups)
-            return sig2, V, lam
-        if _lib.low_rank_estimate_wide_supported(D, m, len(pick), k_max):
-            idx = None if chains is None else torch.as_tensor(np.asarray(chains, dtype=np.int64), device=draws.device)
-            sig2, V, lam, _ = _lib.low_rank_estimate_wide(draws, grads, idx, lo, hi, pick, gamma, cutoff, k_max, max_workgroups)
+            sig2, V, lam, _ = kernel(draws, grads, idx, lo, hi, pick, gamma, cutoff, k_max, max_workgroups)
             return sig2, V, lam
     if chains is None:
         x, g = draws[:, lo:hi], grads[:, lo:hi]
@@ -513,10 +510,8 @@ class LowRankSampler:
             from nutpie_amd import _lib
 
             D = int(self._inner.dim)
-            b = min(basis_draws_for(D), D)
             return bool(NATIVE_ESTIMATOR and torch.cuda.is_available() and hasattr(self._inner, "device_ptr") and
-                        ((_lib.low_rank_estimate_supported(D, WINDOW_MAX, b, K_MAX) and basis_draws_for(D) <= 32) or
-                         _lib.low_rank_estimate_wide_supported(D, WINDOW_MAX, b, K_MAX)))
+                        _lib.low_rank_estimator_for(D, WINDOW_MAX, min(basis_draws_for(D), D), K_MAX) is not None)
         except Exception:  # noqa: BLE001 - (a stand-in engine of the CPU tests)
             return False
 

@@ -1,7 +1,7 @@
 """The fixtures the wide estimator kernel is held to (tests/golden/low_rank_estimator_wide_*.npz, written by
 tests/golden/make_low_rank_reference_wide.py from the 50-digit restatement tests/low_rank_reference.py on the regenerated inputs of
-tests/low_rank_reference_wide.py): the inputs regenerate bit for bit, sit away from every threshold, the fixtures have not rotted, and the
-C-ABI declares and binds the kernel's two entry points."""
+tests/low_rank_reference_wide.py): the inputs regenerate bit for bit, sit away from every threshold, the fixtures have not rotted, the
+C-ABI declares and binds the kernel's two entry points, and every shape goes to the kernel that is to take it."""
 import math
 import os
 import re
@@ -145,3 +145,24 @@ def test_the_header_declares_both_entry_points_and_the_binding_matches():
     assert not ok(1025, 256, 64, 16) and not ok(300, 256, 65, 16) and not ok(300, 1, 1, 16) and not ok(40, 64, 41, 16)
     assert not ok(300, 32, 33, 16) and not ok(300, 256, 64, 17) and not ok(300, 256, 64, 0)
     assert _lib.WIDE_WORKGROUP_SCRATCH == 3 * 1024 + 3 * 128 * 128 + 16 * 128
+
+
+def test_every_shape_the_narrow_kernel_takes_the_wide_one_takes_too_and_the_choice_is_narrow_first():
+    """``low_rank.estimate_window`` and the driver ask ``low_rank_estimator_for``: the narrow kernel where it covers the shape, else the
+    wide one, else neither — over the edges of both kernels' limits (the predicates are host code)."""
+    from nutpie_amd import _lib
+
+    seen = set()
+    for dim in (1, 31, 32, 256, 512, 513, 1024, 1025):
+        for n_pick in (1, 32, 33, 64, 65):
+            for m in (1, 2, 40, 256):
+                for k_max in (0, 1, 16, 17):
+                    shape = (dim, m, n_pick, k_max)
+                    narrow, wide = _lib.low_rank_estimate_supported(*shape), _lib.low_rank_estimate_wide_supported(*shape)
+                    assert wide or not narrow, shape
+                    want = _lib.low_rank_estimate if narrow else _lib.low_rank_estimate_wide if wide else None
+                    assert _lib.low_rank_estimator_for(*shape) is want, shape
+                    seen.add(getattr(want, "__name__", None))
+                    inside = m >= 2 and n_pick <= min(m, dim) and 1 <= k_max <= 16   # the limits as include/nutpie_hip.h states them
+                    assert narrow == (inside and dim <= 512 and n_pick <= 32) and wide == (inside and dim <= 1024 and n_pick <= 64), shape
+    assert seen == {"low_rank_estimate", "low_rank_estimate_wide", None}
