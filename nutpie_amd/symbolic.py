@@ -125,6 +125,44 @@ def _is_number(v) -> bool:
     return isinstance(v, (int, float, np.integer, np.floating))
 
 
+_LGAMMA_DIFF_FROM = 16.0     # Stirling's series through x^-11 is exact to 1.4e-18 from here on
+
+
+def _lgamma_diff(x, d) -> Expr:
+    """lgamma(x + d) - lgamma(x) for x > 0, d >= 0 without subtracting two numbers of size x log x: from x = 16 on the difference of the
+    two Stirling series taken term by term,
+        (x + d - 1/2) log1p(d / x) + d log x - d - d / (12 x (x + d)) + T(x + d) - T(x),
+    T(t) = -1/(360 t^3) + 1/(1260 t^5) - 1/(1680 t^7) + 1/(1188 t^9) - 691/(360360 t^11); below, the plain difference (both terms small).
+    The series branch is evaluated at max(x, 16), so the branch not taken stays finite and its adjoint is an exact zero."""
+    x, d = Expr.wrap(x), Expr.wrap(d)
+    far = x - _LGAMMA_DIFF_FROM
+    xs = select(far, x, _LGAMMA_DIFF_FROM)
+    xd = xs + d
+
+    def tail(t):
+        w = 1.0 / (t * t)
+        return (w / t) * (-1.0 / 360.0 + w * (1.0 / 1260.0 + w * (-1.0 / 1680.0 + w * (1.0 / 1188.0 - w * (691.0 / 360360.0)))))
+
+    series = (xd - 0.5) * log1p(d / xs) + d * log(xs) - d - d / (12.0 * xs * xd) + (tail(xd) - tail(xs))
+    return select(far, series, lgamma(x + d) - lgamma(x))
+
+
+_LOG1P_RATIO_BELOW = 1.0 / 32.0     # the series of w - log1p(w) through w^12 is exact to 3e-18 of its first term below this
+
+
+def _x_log1p_ratio(x, c, small, plain) -> Expr:
+    """x log1p(c / x) where ``small`` > 0 says that c / x < 1/32 (elsewhere ``plain``, the caller's form of the same value): written as
+    c - x k(c / x), k(w) = w - log1p(w) = w^2/2 - w^3/3 + ..., so that the gradient in x, -k(w) + w^2 / (1 + w), is a sum of terms of its
+    own size.  The derivative of x log1p(c / x) itself, log1p(w) - w / (1 + w), loses all digits as x grows: each term is w, the sum
+    w^2 / 2.  c must be finite where ``small`` <= 0 too (the branch not taken is evaluated at w = 0; its adjoint is an exact zero)."""
+    x, c = Expr.wrap(x), Expr.wrap(c)
+    w = select(small, c / x, 0.0)
+    k = 1.0 / 12.0
+    for n in range(11, 1, -1):
+        k = 1.0 / n - w * k
+    return select(small, c - x * ((w * w) * k), plain)
+
+
 def student_t_lpdf(x, nu, mu, sigma) -> Expr:
     """``nu``: a Python number (its log-gamma terms are folded on the host) or an expression (a parameter: ``lgamma`` in the kernel)."""
     x, mu, sigma = Expr.wrap(x), Expr.wrap(mu), Expr.wrap(sigma)
@@ -134,8 +172,11 @@ def student_t_lpdf(x, nu, mu, sigma) -> Expr:
         c = math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi)
         return c - log(sigma) - (0.5 * (nu + 1.0)) * log1p((z * z) / nu)
     nu = Expr.wrap(nu)
-    c = lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * log(nu * math.pi)
-    return c - log(sigma) - (0.5 * (nu + 1.0)) * log1p((z * z) / nu)
+    c = _lgamma_diff(0.5 * nu, 0.5) - 0.5 * log(nu * math.pi)
+    zz = z * z
+    w = zz / nu
+    tail = log1p(w)
+    return c - log(sigma) - 0.5 * _x_log1p_ratio(nu, zz, _LOG1P_RATIO_BELOW - w, nu * tail) - 0.5 * tail
 
 
 def cauchy_lpdf(x, mu, gamma) -> Expr:
@@ -232,8 +273,11 @@ def negative_binomial_log_lpmf(y, eta, phi, log_factorial) -> Expr:
         raise ValueError("negative_binomial_log_lpmf: phi is a parameter or data expression (lgamma(y + phi) depends on the observation)")
     phi = Expr.wrap(phi)
     lphi = log(phi)
-    lse = softplus(eta - lphi) + lphi               # log(mu + phi)
-    return lgamma(y + phi) - lgamma(phi) - Expr.wrap(log_factorial) + y * (eta - lse) + phi * (lphi - lse)
+    # y (eta - log(mu + phi)) and phi (log phi - log(mu + phi)) without forming log(mu + phi): nothing of size phi log phi is subtracted
+    t = eta - lphi                                  # log(mu / phi)
+    small = math.log(_LOG1P_RATIO_BELOW) - t
+    mu = exp(select(small, eta, 0.0))               # (only read where mu / phi is small)
+    return _lgamma_diff(phi, y) - Expr.wrap(log_factorial) - y * softplus(-t) - _x_log1p_ratio(phi, mu, small, phi * softplus(t))
 
 
 def dirichlet_lpdf(p, a) -> Expr:
@@ -353,7 +397,7 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
         elif n.op == "tanh":
             acc(a, g * (1.0 - n * n))
         elif n.op == "expm1":
-            acc(a, g * (n + 1.0))
+            acc(a, g * exp(a))             # (not n + 1: that is absolute, and the derivative is tiny where expm1 is near -1)
         elif n.op == "erf":
             acc(a, g * (_TWO_OVER_SQRT_PI * exp(-(a * a))))
         elif n.op == "erfc":
@@ -367,7 +411,8 @@ def gradient(out: Expr, wrt: list[Expr]) -> list[Expr]:
         elif n.op == "lgamma":
             acc(a, g * digamma(a))
         elif n.op == "digamma":
-            raise NotImplementedError("the derivative of digamma (trigamma) is not available")
+            if any(t.op in ("sparam", "vparam") for t in _topo([a])):      # (digamma of data is a constant of the model)
+                raise NotImplementedError("the derivative of digamma (trigamma) is not available")
         elif n.op == "abs":
             acc(a, g * sign(a))
         elif n.op == "sign":
