@@ -184,9 +184,9 @@ def generated_source(user_source: str, layout) -> str:
     ])
 
 
-def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verbose: bool = False, low_rank: bool = False) -> str:
-    """Build (or find in the cache) the model's library; returns its path.  ``waves`` wavefronts evaluate one chain's density.
-    ``low_rank``: the library's resident kernel integrates under the low-rank metric (``adaptation="low_rank"``)."""
+def library_key(user_source: str, layout, ndim: int, *, waves: int = 1, low_rank: bool = False) -> tuple[str, str, list[str]]:
+    """(the cache key of the model's library, the full source, the compiler flags): the key hashes the source, the engine's files, the
+    chain headers the source includes (``chain_headers``) and the flags — nothing is compiled"""
     if waves not in (1, 2, 4):
         raise ValueError("waves_per_chain must be 1, 2 or 4")
     nv = ((int(ndim) + 127) // 128 + waves - 1) // waves   # chunks of 128 dimensions per wave
@@ -203,7 +203,14 @@ def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verb
     flags = (_FLAGS + ["-mllvm", "-enable-ipra=0", "-DNPHIP_JIT_DENSITY=1", "-DNPHIP_PART=7", f"-DNPHIP_JIT_NV={max(1, nv)}", f"-DNPHIP_JIT_W={waves}"]
              + (["-DNPHIP_JIT_LR=1"] if low_rank else []) + os.environ.get("NUTPIE_AMD_JIT_FLAGS", "").split())
     h.update(" ".join(flags).encode())
-    out = os.path.join(cache_dir(), f"density_{h.hexdigest()[:24]}.so")
+    return h.hexdigest()[:24], src, flags
+
+
+def compile_density(user_source: str, layout, ndim: int, *, waves: int = 1, verbose: bool = False, low_rank: bool = False) -> str:
+    """Build (or find in the cache) the model's library; returns its path.  ``waves`` wavefronts evaluate one chain's density.
+    ``low_rank``: the library's resident kernel integrates under the low-rank metric (``adaptation="low_rank"``)."""
+    key, src, flags = library_key(user_source, layout, ndim, waves=waves, low_rank=low_rank)
+    out = os.path.join(cache_dir(), f"density_{key}.so")
     if os.path.exists(out):
         return out
     # (the temporary directory lives INSIDE the cache directory: os.replace below must not cross a filesystem — /tmp often is a tmpfs)

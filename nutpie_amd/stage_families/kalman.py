@@ -4,6 +4,8 @@
 [, obs]) its adjoint — what the gradient emits, with the adjoints of the stored v and F that the IR's own loops compute as stored
 operands.  Each packs its arrays on a dimension of its own: [apred: R T m | Ppred: R T m m | afilt: R T m | v: R T | F: R T] resp.
 [ybar: R T | hbar: R T | Zbar: R T m | Tbar: m m | Qbar: m m | a0bar: m | P0bar: m m | per-series partials: R (3 m m + m)];
+``kalman_smooth`` (args Z, Tm, the forward result [, obs]) is the fixed-interval smoother of ``csrc/kalman_smoother.h``, run by the expand
+step only: it packs [asm: R T m | vsm: R T m], the smoothed state means and variances, on a third dimension and carries no gradient.
 ``kalman_part`` (payload: the offset) reads one of them as a value on the dimension it belongs to, like ``hmm_part``.
 payload = (R, T, m, masked)."""
 
@@ -17,7 +19,8 @@ from nutpie_amd.expr import _HALF_LOG_2PI, Dim, Expr, _bcast, _segsum, log
 from nutpie_amd.stage_families import Family, np_part, read_part
 from nutpie_amd.trace_values import UnsupportedTorchOp, _numel, _Sym
 
-_KALOPS = ("kalman_fwd", "kalman_bwd")
+_KALOPS = ("kalman_fwd", "kalman_bwd", "kalman_smooth")
+SMOOTHER_HEADER = "kalman_smoother.h"
 MAX_KALMAN_STATE = 8   # a lane keeps its row of the state covariance in registers, a group of up to 8 lanes owns a series
 
 
@@ -59,6 +62,15 @@ def _kalman_forward(y, Z, h, Tm, Q, a0, P0, obs, R: int, T: int, m: int, what: s
 def _kalman_backward(F: Expr, vbar: Expr, Fbar: Expr) -> Expr:
     y, Z, h, Tm, Q = F.args[:5]
     return Expr("kalman_bwd", (y, Z, h, Tm, Q, F, vbar, Fbar) + F.args[7:], F.dim._kalman_back, F.payload)
+
+
+def _kalman_smooth(F: Expr) -> Expr:
+    """the smoother stage over the filter stage ``F``, on the dimension ``<steps>__kf_s`` (named after the shape where ``F``'s is)"""
+    R, T, m, _ = F.payload
+    Z, Tm = F.args[1], F.args[3]
+    model = F.dim._model()
+    packed = model.dim(F.dim.name.replace("__kf_f", "__kf_s"), 2 * R * T * m)
+    return Expr("kalman_smooth", (Z, Tm, F) + F.args[7:], packed, F.payload)
 
 
 def _kalman_part(X: Expr, offset: int, dim: Dim) -> Expr:
@@ -140,11 +152,26 @@ def kalman_filtered_state(y, *, design, obs_var, transition, state_cov, init_mea
     return _kalman_part(F, 0 if predicted else R * T * (m + m * m), out)
 
 
+def kalman_smoothed_state(y, *, design, obs_var, transition, state_cov, init_mean, init_cov, observed=None, along: str | None = None,
+                          variance: bool = False) -> Expr:
+    """The mean of the state at every step given ALL the observations of its series (``variance``: the variance of every state
+    element, the diagonal of the smoothed covariance), a value on ``product(y.dim, state)``: the posterior of the latent path that
+    ``kalman_marginal_lpdf`` sums out, by the fixed-interval smoother (the backward recursion of de Jong / Durbin & Koopman over
+    what the filter stored).  On trailing steps with ``observed = 0`` these are the forecast and its variance.  Meant for
+    ``Model.deterministic``: with the same arguments as the model's ``kalman_marginal_lpdf`` it reads the filter stage the density
+    has, and mean and variance share one smoother stage, which only the expand step runs.  It carries no gradient."""
+    *args, R, T, m, state = _kalman_args(y, design, obs_var, transition, state_cov, init_mean, init_cov, observed, along, "kalman_smoothed_state")
+    F = _kalman_forward(*args, R, T, m, what="kalman_smoothed_state")
+    steps = F.args[0].dim
+    out = steps._model().product(steps.name, state.name)
+    return _kalman_part(_kalman_smooth(F), R * T * m if variance else 0, out)
+
+
 # ---- reverse mode: the adjoints of the stored v and F arrive through their readers, one after the other; the filter's own adjoint is ONE
 # backward stage that takes both, built when the traversal reaches the filter node (every reader has been visited by then)
 def _part_adjoint(n: Expr, g: Expr, ad):
     a = n.args[0]
-    if a.op != "kalman_fwd":
+    if a.op != "kalman_fwd":       # (the adjoint's own parts; the smoother's: kalman_smoothed_state carries no gradient)
         return False
     R, T, m, _ = a.payload
     if n.payload < R * T * (2 * m + m * m):       # (the state means: kalman_filtered_state carries no gradient)
@@ -166,14 +193,42 @@ def _finish(n: Expr, parts: dict, ad):
 
 # ---- host evaluation
 def _np_kalman(op: str, args: list[np.ndarray], R: int, T: int, m: int, masked: bool, N: int) -> np.ndarray:
-    """the packed result of the filter (``kalman_fwd``) or its adjoint (``kalman_bwd``) by the plain sequential algorithm in matrix form,
-    in the precision of its arguments: the checker (the bitwise reference of the device routines is tests/fixtures/kalman_reference.c)"""
+    """the packed result of the filter (``kalman_fwd``), its adjoint (``kalman_bwd``) or the smoother (``kalman_smooth``) by the plain
+    sequential algorithm in matrix form, in the precision of its arguments: the checker (the bitwise references of the device routines
+    are tests/fixtures/kalman_reference.c and kalman_smoother_reference.c)"""
     dt = np.result_type(*args)
 
     def full(v, *shape):
         v = np.asarray(v)
         return np.broadcast_to(v[:, None] if v.ndim == 1 else v, (N, int(np.prod(shape)))).reshape(N, *shape)
 
+    def unpack(F):
+        cuts = np.cumsum([R * T * m, R * T * m * m, R * T * m, R * T])
+        return (v_.reshape(N, R, T, *sh) for v_, sh in zip(np.split(np.asarray(F), cuts, axis=1), ((m,), (m, m), (m,), (), ())))
+
+    if op == "kalman_smooth":
+        # the backward recursion of de Jong / Durbin & Koopman: r and N gather what the later steps say about the state at t
+        Z, Tm = full(args[0], R, T, m), full(args[1], m, m)
+        apred, Ppred, _, vs, Fs = unpack(args[2])
+        obs = full(args[3], R, T) != 0 if masked else np.ones((N, R, T), bool)
+        r, Nm = np.zeros((N, R, m), dt), np.zeros((N, R, m, m), dt)
+        mean, var = np.empty((N, R, T, m), dt), np.empty((N, R, T, m), dt)
+        for t in range(T - 1, -1, -1):
+            z, seen, a, P, v, Fv = Z[:, :, t], obs[:, :, t], apred[:, :, t], Ppred[:, :, t], vs[:, :, t], Fs[:, :, t]
+            if t < T - 1:
+                u, W = np.einsum("nik,nri->nrk", Tm, r), np.einsum("nli,nrlj,njk->nrik", Tm, Nm, Tm)
+            else:
+                u, W = np.zeros_like(r), np.zeros_like(Nm)
+            K = np.einsum("nrij,nrj->nri", P, z) / Fv[..., None]
+            e = v / Fv - np.einsum("nri,nri->nr", K, u)
+            g, gt = np.einsum("nrij,nrj->nri", W, K), np.einsum("nrij,nri->nrj", W, K)
+            D = 1.0 / Fv + np.einsum("nri,nri->nr", K, g)
+            zz = z[..., :, None] * z[..., None, :]
+            r = np.where(seen[..., None], u + e[..., None] * z, u)
+            Nm = np.where(seen[..., None, None], W - z[..., :, None] * gt[..., None, :] - g[..., :, None] * z[..., None, :] + D[..., None, None] * zz, W)
+            mean[:, :, t] = a + np.einsum("nrij,nrj->nri", P, r)
+            var[:, :, t] = np.einsum("nrii->nri", P) - np.einsum("nrij,nrjk,nrik->nri", P, Nm, P)
+        return np.concatenate([mean.reshape(N, -1), var.reshape(N, -1)], axis=1)
     y, Z, h, Tm, Q = full(args[0], R, T), full(args[1], R, T, m), full(args[2], R, T), full(args[3], m, m), full(args[4], m, m)
     fwd = op == "kalman_fwd"
     obs = full(args[7 if fwd else 8], R, T) != 0 if masked else np.ones((N, R, T), bool)
@@ -195,9 +250,7 @@ def _np_kalman(op: str, args: list[np.ndarray], R: int, T: int, m: int, masked: 
             a = np.einsum("nik,nrk->nri", Tm, af)
             P = Q[:, None] + np.einsum("nik,nrkl,njl->nrij", Tm, Pf, Tm)
         return np.concatenate([v_.reshape(N, -1) for v_ in (apred, Ppred, afilt, vs, Fs)], axis=1)
-    F = np.asarray(args[5])
-    cuts = np.cumsum([R * T * m, R * T * m * m, R * T * m, R * T])
-    apred, Ppred, _, vs, Fs = (v_.reshape(N, R, T, *sh) for v_, sh in zip(np.split(F, cuts, axis=1), ((m,), (m, m), (m,), (), ())))
+    apred, Ppred, _, vs, Fs = unpack(args[5])
     vbar, Fbar = full(args[6], R, T), full(args[7], R, T)
     ybar, hbar, Zbar = np.zeros((N, R, T), dt), np.zeros((N, R, T), dt), np.zeros((N, R, T, m), dt)
     Tb, Qb = np.zeros((N, R, m, m), dt), np.zeros((N, R, m, m), dt)
@@ -243,6 +296,9 @@ def _call(gen, n: Expr) -> str:
     if n.op == "kalman_fwd":
         y, Z, h, Tm, Q, a0, P0 = n.args[:7]
         return f"    nphip_kalman::forward<{shape}>({name(y)}, {obs}, {name(Z)}, {name(h)}, {name(Tm)}, {name(Q)}, {name(a0)}, {name(P0)}, {name(n)}, lane);"
+    if n.op == "kalman_smooth":
+        Z, Tm, F = n.args[:3]
+        return f"    nphip_kalman::smooth<{shape}>({obs}, {name(Z)}, {name(Tm)}, {name(F)}, {name(n)}, lane);"
     y, Z, h, Tm, Q, F, vbar, Fbar = n.args[:8]
     return (f"    nphip_kalman::backward<{shape}>({name(y)}, {obs}, {name(Z)}, {name(h)}, {name(Tm)}, {name(Q)}, {name(F)}, {name(vbar)}, {name(Fbar)}, "
             f"{name(n)}, lane);")
@@ -250,6 +306,11 @@ def _call(gen, n: Expr) -> str:
 
 def _section(n: Expr) -> str:
     return f"stage {n.op}<{', '.join(str(int(v)) for v in n.payload)}>"
+
+
+def _includes(nodes) -> list[str]:
+    """a source that runs the smoother (an expand function) includes its header beside the filter's"""
+    return [FAMILY.header] + ([SMOOTHER_HEADER] if any(n.op == "kalman_smooth" for n in nodes) else [])
 
 
 def _check(nodes, waves_per_chain):
@@ -433,5 +494,6 @@ def _torch_kalman_marginal(c):
 
 FAMILY = Family(name="kalman", ops=_KALOPS, readers=("kalman_part",), header="chain_kalman.h", header_deps=("chain_hmm.h",), call=_call,
                 read=read_part, numpy=_numpy, adjoint={"kalman_part": _part_adjoint}, finish=_finish,
-                refusal="second derivatives of the Kalman filter stages (kalman_filtered_state carries no gradient)",
+                refusal="second derivatives of the Kalman filter stages (kalman_filtered_state and kalman_smoothed_state carry no gradient)",
+                more_headers=(SMOOTHER_HEADER,), includes=_includes,
                 check=_check, section=_section, series_lengths=_series_lengths, torch_rules={"kalman_marginal": _torch_kalman_marginal})

@@ -41,7 +41,9 @@ routine runs on the chain's wave(s) (``csrc/chain_hmm.h``), K 
 Linear Gaussian state-space models: ``kalman_marginal_lpdf(y, design=, obs_var=, transition=, state_cov=, init_mean=, init_cov=,
 observed=None, along=None)`` sums the latent state out with a Kalman filter, ``kalman_filtered_state`` reports the filtered or predicted
 state means — a stage between loops that one device routine runs on the chain's wave(s) (``csrc/chain_kalman.h``),
-state dimension <= 8, up to four waves per chain.
+state dimension <= 8, up to four waves per chain.  ``kalman_smoothed_state`` reports the posterior of the path that was summed out: the
+mean and (``variance=True``) the variance of the state at every step given all the observations, forecasts on trailing missing steps
+included — a fixed-interval smoother that the expand step runs over the stored draws (``csrc/kalman_smoother.h``).
 
 Also: ``m.matrix("X", values, dim="obs", cols="coef")`` and ``X @ beta`` (a design matrix: with up to 63 columns lowered to a sum over
 its columns, the transposed product to one wave-wide sum per column; with more — or ``stage=True``, or a ``B`` with several right-hand
@@ -83,7 +85,7 @@ __all__ = ["Model", "Expr", "Matrix", "exp", "log", "log1p", "sqrt", "softplus",
            "bernoulli_logit_lpmf", "binomial_logit_lpmf", "negative_binomial_log_lpmf", "poisson_log_lpmf", "dirichlet_lpdf", "flat_lpdf",
            "cholesky", "solve_lower", "log_det_chol", "mvnormal_lpdf", "lkj_corr_cholesky_lpdf",
            "linear_recurrence", "cumsum", "column", "pack_columns", "hmm_marginal_lpdf", "hmm_state_prob",
-           "kalman_marginal_lpdf", "kalman_filtered_state"]
+           "kalman_marginal_lpdf", "kalman_filtered_state", "kalman_smoothed_state"]
 
 _WAVE = 64
 _SEG_BATCH = os.environ.get("NUTPIE_AMD_SEG_MODE", "select") != "loop"   # (developer switch: "loop" = plain loops over a segment)
@@ -100,7 +102,8 @@ from nutpie_amd.stage_families import _READERS, _STAGES, FAMILIES, family_of, ha
 from nutpie_amd.stage_families.hmm import (MAX_HMM_STATES, _HMMOPS, _hmm_backward, _hmm_forward, _hmm_lpdf, _hmm_model, _hmm_part, _hmm_prob,  # noqa: F401
                                            _hmm_shape, _np_hmm, hmm_marginal_lpdf, hmm_state_prob)
 from nutpie_amd.stage_families.kalman import (MAX_KALMAN_STATE, _KALOPS, _kalman_args, _kalman_backward, _kalman_forward, _kalman_part,  # noqa: F401
-                                              _kalman_sizes, _kalman_terms, _np_kalman, kalman_filtered_state, kalman_marginal_lpdf)
+                                              _kalman_sizes, _kalman_terms, _np_kalman, kalman_filtered_state, kalman_marginal_lpdf,
+                                              kalman_smoothed_state)
 from nutpie_amd.stage_families.linalg import (MAX_MATRIX, _MATOPS, _lkj_log_norm, _np_chol, _np_matop, _np_solve_lower, _np_solve_lower_t, _side,  # noqa: F401
                                               cholesky, lkj_corr_cholesky_lpdf, log_det_chol, mvnormal_lpdf, solve_lower)
 from nutpie_amd.stage_families.matvec import MAX_RHS, _MVOPS, Matrix, _MatrixT, column, pack_columns  # noqa: F401

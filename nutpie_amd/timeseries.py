@@ -13,7 +13,8 @@ through ``from_torchfunc``, or traced with :func:`nutpie_amd.torch_trace.trace`)
   algorithm (``symbolic.hmm_marginal_lpdf``); ordered state means, one scale, a transition matrix of simplex rows.
   Vector: ``[mu_ordered__ (K), sigma_log__, P_0_simplex__ (K - 1), ..., P_{K-1}_simplex__ (K - 1)]``.
 * :func:`local_linear_trend_model` — a structural time series (level + slope, optionally one trigonometric seasonal harmonic) with the
-  state summed out by a Kalman filter (``symbolic.kalman_marginal_lpdf``); a share of the steps is missing.
+  state summed out by a Kalman filter (``symbolic.kalman_marginal_lpdf``, DESIGN.md §11.9); a share of the steps is missing;
+  ``smoothed=True`` reports the smoothed level and its standard deviation (``symbolic.kalman_smoothed_state``), forecasts included.
   Vector: ``[sigma_obs_log__, sigma_level_log__, sigma_slope_log__ (, sigma_seasonal_log__)]``.
 * :func:`ar_p_model` — AR(p) in companion form observed with noise: the transition matrix depends on the parameters.
   Vector: ``[rho (p), sigma_log__, tau_log__]``.
@@ -309,13 +310,21 @@ def synthetic_trend(T: int = 200, seasonal_period=None, R: int = 1, missing: flo
     return y, observed
 
 
-def local_linear_trend_model(T: int = 200, seasonal_period=None, R: int = 1, missing: float = 0.1, seed: int = 0) -> S.Model:
+def local_linear_trend_model(T: int = 200, seasonal_period=None, R: int = 1, missing: float = 0.1, seed: int = 0, smoothed: bool = False,
+                             forecast: int = 0) -> S.Model:
     """level_{t+1} = level_t + slope_t + sigma_level e, slope_{t+1} = slope_t + sigma_slope e (``seasonal_period``: plus one
     trigonometric harmonic with disturbances sigma_seasonal; the state then has four elements), y_t = level_t (+ seasonal_t) +
     sigma_obs e; every scale ~ HalfNormal(1); the state at t = 0 ~ N(0, diag(100, 1 (, 25, 25))); a share ``missing`` of the steps is
     not observed.  The state is summed out: ``kalman_marginal_lpdf``.  ``R`` > 1: a panel of R series that share the parameters.
-    Deterministic ``filtered_level``: the filtered mean of the level at every step (``[R T]``)."""
+    Deterministic ``filtered_level``: the filtered mean of the level at every step (``[R T]``).
+    ``smoothed``: also ``smoothed_level`` and ``smoothed_level_sd``, the mean and the standard deviation of the level at every step
+    given ALL the observations of its series (``kalman_smoothed_state``): the posterior of the path that was summed out.  Forecasts
+    with their variances are the smoothed values on trailing steps with ``observed = 0`` — ``forecast`` appends that many steps to
+    every series (the time axis then has ``T + forecast`` elements; their ``y`` is never read)."""
     y, observed = synthetic_trend(T, seasonal_period, R, missing, seed)
+    if forecast:
+        y, observed = (np.concatenate([v, np.zeros((R, int(forecast)))], axis=1) for v in (y, observed))
+        T += int(forecast)
     Tm, z, p0 = _trend_matrices(seasonal_period)
     k = z.size
     m = S.Model()
@@ -340,6 +349,9 @@ def local_linear_trend_model(T: int = 200, seasonal_period=None, R: int = 1, mis
     obs = m.data("y", y.reshape(-1), dim=steps)
     m.add_logp(S.kalman_marginal_lpdf(obs, **args))
     m.deterministic("filtered_level", S.column(S.kalman_filtered_state(obs, **args), 0))
+    if smoothed:
+        m.deterministic("smoothed_level", S.column(S.kalman_smoothed_state(obs, **args), 0))
+        m.deterministic("smoothed_level_sd", S.sqrt(S.column(S.kalman_smoothed_state(obs, variance=True, **args), 0)))
     return m
 
 
